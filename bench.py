@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's headline metric on synthetic Lyft-shape input.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no launcher in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank
@@ -17,7 +17,13 @@ resident in HBM -- the live frame and the 10 x 36 history frames sit in the fram
 history: PP score (descriptor table -> pose fused into the neighbour count, ~10.8 M history points)
 -> RANSAC ground plane -> plane/range mask -> PP-weighted mutual-kNN DBSCAN -> cluster filter ->
 closeness box fit -> BEV IoU NMS -> KITTI label text.  value = scans/s over all ranks (weak scaling:
-every rank processes K scans of its own).  Besides the contract fields the JSON line carries
+every rank processes K scans of its own); ms_per_step = the timed region's wall time / K.
+
+A plain run sets up, warms up, times the K steps and prints the line (contract fields + `config`).
+--dump-outputs DIR also writes what the last timed step computed (the last step of the last helper's share) as
+DIR/<name>.npy after the clock: pp_score (N,) float32, cluster_labels (N,) and boxes (k, 8) {t0, t1, t2, l, w, h, ry,
+volume} float64, label_fields (k, 14) float64 = the numeric fields of the KITTI label lines; with the same arguments
+the inputs are the same seeded synthetic scans from run to run.  Only with --full the JSON line also carries
   roofline     -- the PP neighbour count (the operation SURVEY.md 8d prices at 12*M + 16*N
                   algorithmic bytes per scan; here it is a chain of kernels, so the WHOLE chain is
                   timed with HIP events, not just its largest kernel) against the 8 TB/s HBM3E peak, on a
@@ -34,8 +40,11 @@ every rank processes K scans of its own).  Besides the contract fields the JSON 
                   solves the 361 relative poses from the raw pose factors and builds its descriptor table
                   from scratch: `value` without the "already resident and described" head start;
   cli          -- the three product CLIs (pre_compute_pp_score, generate_mask, gen_label_files) on a
-                  synthetic KITTI tree with shared history frames, file I/O included; rank 0, N=1.
-Nothing here reads /root/reference.
+                  synthetic KITTI tree with shared history frames, file I/O included; rank 0, N=1;
+  steady_state -- the whole helper pool over 24 steps per helper when K gives the helpers fewer (see below);
+  parity       -- the measured path against the oracle on the CPU sample's scans.
+Without --full these keys are null.
+Nothing here reads the reference project's sources.
 """
 from __future__ import annotations
 
@@ -61,7 +70,7 @@ HBM_PEAK_GBPS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s sp
 # is dealt: few helpers carry long chains of stages 2 + 3 on their host side, many helpers run many small PP blocks one after
 # the other on the GPU (a block of 4 / 7 / 10 scans costs 0.74 / 0.79 / 0.90 ms).  Measured with the round-5 kernels, three runs
 # each (tools/r05_steps20.sh): 5 x 4 scans 2 620-3 020 scans/s, 4 x 5 2 540-2 770, 3 x 6-7 2 750-3 010, 2 x 10 2 640-2 840.
-# A run with fewer than STEADY_STEPS_PER_HELPER steps per helper also reports `steady_state`: the whole pool over 24 steps per
+# A --full run with fewer than STEADY_STEPS_PER_HELPER steps per helper also reports `steady_state`: the whole pool over 24 steps per
 # helper, measured after the contract region with its own barrier / synchronise bracket.
 MIN_STEPS_PER_HELPER = int(os.environ.get("MODEST_MIN_STEPS_PER_HELPER", "6"))
 STEADY_STEPS_PER_HELPER = 24
@@ -131,6 +140,13 @@ def parse(argv=None):
                     help="worker processes per GPU of the CLI measurement's workers=N legs (profiles/r06_cli_workers_readers.txt: "
                          "5-6 workers x 2 reader threads is where the ingest-bound CLIs peak; 8 lose a fifth to the contention of "
                          "their reads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: steady state, value_with_ingest, the "
+                         "isolated PP roofline (best case and realistic windows), the CLI leg, the CPU baselines and the parity "
+                         "check against the oracle.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     a = ap.parse_args(argv)
     a.nusc = a.config == "c5"
     if a.nusc:
@@ -447,8 +463,9 @@ class Runner:
             i = e
         return out
 
-    def run(self, lo, hi, collect=None):
-        """steps lo..hi-1: the blocks are dealt round-robin to the worker threads"""
+    def run(self, lo, hi, collect=None, only=None):
+        """steps lo..hi-1: the blocks are dealt round-robin to the worker threads; collect: list that receives
+        (step, (H, labels, objs, text)) of every step, or of step `only` alone"""
         errs = []
         blocks = self.blocks_of(lo, hi)
 
@@ -493,7 +510,7 @@ class Runner:
                             hook = (lambda b1=bi + 1: enqueue(b1)) if (self.prefetch and last and bi + 1 < len(mine)) else None
                             out = self.steps(cj, w, [Hq.pop(j) for j in cj], after=hook)
                             if collect is not None:
-                                collect.extend(zip(cj, out))
+                                collect.extend((j, o) for j, o in zip(cj, out) if only is None or j == only)
                     self.streams[w].synchronize()
             except Exception as e:   # surfaced after join
                 errs.append(e)
@@ -534,17 +551,20 @@ class Runner:
         self.ingest = False
         self._ingest_rehearsed = True
 
-    def timed(self, n_steps, ingest=False):
-        """n_steps steps -> (seconds, HIP-event times of every PP stage launched)"""
+    def timed(self, n_steps, ingest=False, keep_last=False):
+        """n_steps steps -> (seconds, HIP-event times of every PP stage launched); keep_last: the last step's
+        (H, labels, objs, text) stay in self.last_out"""
         self.ingest = bool(ingest)
         for w, c_ in enumerate(self.pp_ctxs):
             c_.profile_begin(n_steps + 8)
             self.mark_batch[w] = []
         calls0 = (getattr(self.store, "block_calls", 0), getattr(self.store, "chain_calls", 0))
+        last = [] if keep_last else None
         t0 = time.perf_counter()
-        self.run(self.n_warm, self.n_warm + n_steps)
+        self.run(self.n_warm, self.n_warm + n_steps, collect=last, only=self.n_warm + n_steps - 1)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        self.last_out = last[-1][1] if last else None
         self.ingest = False
         # which PP path ran INSIDE the clock: calls of modest_pp_score_block / modest_pp_score_frames_batch and their scans
         self.last_paths = dict(block_calls=getattr(self.store, "block_calls", 0) - calls0[0],
@@ -625,11 +645,11 @@ def scan_seed(rank, slot, i):
 
 def _helper_main(conn, a, rank, local, slot, flag):
     """entry point of a helper process (multiprocessing 'spawn'): pipe protocol
-    child -> ('ready', M) ; parent -> ('arm', (n_steps, generation, ingest mode)) ; child -> ('armed', None), then spins
-    on the shared start flag (all helpers leave the spin within microseconds of each other: a pipe
+    child -> ('ready', M) ; parent -> ('arm', (n_steps, generation, ingest mode, keep last step)) ; child -> ('armed', None),
+    then spins on the shared start flag (all helpers leave the spin within microseconds of each other: a pipe
     message per helper staggers them by ~0.1 ms each, which a 20-step run cannot afford) ;
-    child -> ('done', (seconds, kernel_ms)) ; parent -> ('iso', None) -> child ('iso', ms) ;
-    parent -> ('exit', None)"""
+    child -> ('done', (seconds, kernel_ms)) ; parent -> ('outputs', None) -> child ('outputs', step_arrays of the last step) ;
+    parent -> ('iso', None) -> child ('iso', ms) ; parent -> ('exit', None)"""
     try:
         import resource
         t_up = time.perf_counter()
@@ -638,7 +658,7 @@ def _helper_main(conn, a, rank, local, slot, flag):
         while True:
             cmd, arg = conn.recv()
             if cmd == "arm":
-                n, gen, ingest = arg
+                n, gen, ingest, keep = arg
                 r.rehearse(int(n))
                 if ingest:
                     r.rehearse_ingest()
@@ -653,7 +673,7 @@ def _helper_main(conn, a, rank, local, slot, flag):
                     pass
                 r.trace = [] if os.environ.get("MODEST_BENCH_TRACE") else None
                 seg0 = torch.cuda.memory_stats().get("segment.all.allocated", 0) if r.trace is not None else 0
-                dt, kms = r.timed(int(n), ingest=ingest)
+                dt, kms = r.timed(int(n), ingest=ingest, keep_last=keep)
                 if r.trace is not None:
                     r.trace.append(("torch_segments_allocated_x1000", 1.0 * (torch.cuda.memory_stats().get("segment.all.allocated", 0) - seg0)))   # diagnostics: where a helper's share of the timed region went (host wall time)
                     print(f"[helper {slot}] {n} steps {dt * 1e3:.2f} ms: " + " ".join(f"{k} {v * 1e3:.2f}" for k, v in r.trace),
@@ -661,6 +681,8 @@ def _helper_main(conn, a, rank, local, slot, flag):
                     r.trace = None
                 gc.enable()
                 conn.send(("done", (dt, kms.tolist(), r.last_paths)))
+            elif cmd == "outputs":
+                conn.send(("outputs", step_arrays(r.last_out) if r.last_out is not None else None))
             elif cmd == "iso":
                 conn.send(("iso", r.isolated_pp_ms()))
             elif cmd == "iso_realistic":
@@ -681,6 +703,44 @@ def _split(n, parts):
 def helper_count(procs: int, steps: int) -> int:
     """Helpers actually used: every one gets at least MIN_STEPS_PER_HELPER steps."""
     return max(1, min(procs, steps // MIN_STEPS_PER_HELPER))
+
+
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_CAP_BYTES = 64 << 20
+LABEL_FIELDS = 14   # "Dynamic -1 -1" + alpha, 2-D box (4), h, w, l, t (3), ry: every field after the class name
+
+
+def label_fields(text):
+    """KITTI label text -> (k, 14) float64, the numeric fields of every line"""
+    rows = [[float(v) for v in line.split()[1:]] for line in text.splitlines() if line.strip()]
+    return np.asarray(rows, dtype=np.float64).reshape(-1, LABEL_FIELDS)
+
+
+def step_arrays(out):
+    """what a caller of the timed path receives for one scan, (H, labels, objs, text), as float arrays -> {name: array}"""
+    H, labels, objs, text = out
+    res = {"pp_score": H.detach().cpu().numpy() if torch.is_tensor(H) else np.asarray(H)}
+    if labels is not None:   # (--pp-only: the PP score is all the step computes)
+        res["cluster_labels"] = np.asarray(labels)
+        res["boxes"] = np.asarray(objs).reshape(-1, 8)
+        res["label_fields"] = label_fields(text)
+    return {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in res.items()}
+
+
+def write_outputs(d, arrays, cap=DUMP_CAP_BYTES):
+    """DIR/<name>.npy for every array.  Over `cap` bytes in all, the per-point arrays (pp_score, cluster_labels) keep a
+    fixed, seeded sample of their points, whose indices are written as point_index."""
+    per_point = [k for k in ("pp_score", "cluster_labels") if k in arrays]
+    n = len(arrays["pp_score"])
+    if sum(v.nbytes for v in arrays.values()) > cap:
+        rest = sum(v.nbytes for k, v in arrays.items() if k not in per_point)
+        row = 8 + sum(arrays[k].itemsize for k in per_point)   # (+ the float64 point index)
+        idx = np.sort(np.random.RandomState(0).choice(n, max(0, min(n, (cap - rest) // row)), replace=False))
+        arrays = dict(arrays, point_index=idx.astype(np.float64), **{k: arrays[k][idx] for k in per_point})
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 # --------------------------------------------------------------------------- CPU baselines
@@ -848,9 +908,15 @@ def main():
             print(f"[bench] rank {rank}: {a.procs} helper processes x {ws} ranks exceed the host's {os.cpu_count()} threads: {fit} per rank", file=sys.stderr)
             a.procs = fit
     n_procs = helper_count(a.procs, a.steps)
-    n_pool = max(1, a.procs)
+    deal = os.environ.get("MODEST_WINDOW_DEAL")   # (experiments: "8,6,4,2" = the contract region's scans per helper)
+    shares = None
+    if deal and sum(int(x) for x in deal.split(",")) == a.steps and len(deal.split(",")) <= max(1, a.procs):
+        shares = [int(x) for x in deal.split(",")]
+        n_procs = len(shares)
+    # the helpers beyond the contract region's serve the steady-state region of --full alone: a plain run starts none of them
+    n_pool = max(1, a.procs) if a.full else n_procs
     flag = None
-    if n_pool > 1:
+    if a.procs > 1:
         import multiprocessing as mp
         ctx = mp.get_context("spawn")
         flag = ctx.Value("i", 0, lock=False)
@@ -885,10 +951,11 @@ def main():
     startup["pool_seconds"] = round(time.perf_counter() - t_start, 2)   # until every helper (or the in-process runner) is ready
     generation = [0]
 
-    def timed_region(active, shares, ingest=False):
-        """barrier + synchronise, the helpers run their shares, synchronise + barrier; rank wall clock"""
-        for (p, pc), n in zip(active, shares):
-            pc.send(("arm", (n, generation[0] + 1, ingest)))
+    def timed_region(active, shares, ingest=False, keep_last=False):
+        """barrier + synchronise, the helpers run their shares, synchronise + barrier; rank wall clock.  keep_last: the last
+        helper keeps its last step's outputs (('outputs', None) after the region)"""
+        for q, ((p, pc), n) in enumerate(zip(active, shares)):
+            pc.send(("arm", (n, generation[0] + 1, ingest, keep_last and q == len(active) - 1)))
         for p, pc in active:
             tag, msg = pc.recv()
             if tag != "armed":
@@ -936,21 +1003,16 @@ def main():
             return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
 
     cpu0 = host_cpu_seconds()
+    dump = bool(a.dump_outputs) and rank == 0
     if helpers:
-        deal = os.environ.get("MODEST_WINDOW_DEAL")   # (experiments: "8,6,4,2" = the contract region's scans per helper)
-        if deal and sum(int(x) for x in deal.split(",")) == a.steps and len(deal.split(",")) <= n_pool:
-            shares = [int(x) for x in deal.split(",")]
-            n_procs = len(shares)
-        else:
-            shares = _split(a.steps, n_procs)
-        dt, kernel_ms = timed_region(helpers[:n_procs], shares)
+        dt, kernel_ms = timed_region(helpers[:n_procs], shares or _split(a.steps, n_procs), keep_last=dump)
         paths = timed_region.paths
     else:
         runner.rehearse(a.steps)
         torch.cuda.synchronize()
         dist.barrier()
         t0 = time.perf_counter()
-        _, kernel_ms = runner.timed(a.steps)
+        _, kernel_ms = runner.timed(a.steps, keep_last=dump)
         torch.cuda.synchronize()
         dist.barrier()
         dt = time.perf_counter() - t0
@@ -959,6 +1021,18 @@ def main():
     # its helpers inside the contract clock / the clock (a polling helper counts as one whether or not it has work), resident memory
     mine = dict(rank=rank, busy_threads=round((host_cpu_seconds() - cpu0) / max(dt, 1e-9), 2), rss_mb=round(host_rss_mb(), 1),
                 processes=1 + len(helpers))
+    if dump:   # the last step of the contract region (with helpers: the last step of the last helper's share)
+        outputs = None
+        if helpers:
+            helpers[n_procs - 1][1].send(("outputs", None))
+            tag, outputs = helpers[n_procs - 1][1].recv()
+            if tag != "outputs":
+                raise RuntimeError(f"helper process failed: {outputs}")
+        elif runner.last_out is not None:
+            outputs = step_arrays(runner.last_out)
+        if outputs is None:
+            raise RuntimeError("--dump-outputs: the timed region ran no step")
+        write_outputs(a.dump_outputs, outputs)
     host_budget = [mine]
     if ws > 1 and torch.distributed.is_initialized():
         host_budget = [None] * ws
@@ -966,7 +1040,7 @@ def main():
     red = dist.reduce_counters(dict(max_seconds=dt, scans=a.steps))
     dt_max, total_scans = red["max_seconds"], red["scans"]
     steady = None
-    if helpers and (n_procs < n_pool or a.steps < STEADY_STEPS_PER_HELPER * n_pool):   # few steps: also report the pool's steady state
+    if a.full and helpers and (n_procs < n_pool or a.steps < STEADY_STEPS_PER_HELPER * n_pool):   # few steps: also the pool's steady state
         n_ss = STEADY_STEPS_PER_HELPER * n_pool
         dt_ss, _ = timed_region(helpers, _split(n_ss, n_pool))
         red_ss = dist.reduce_counters(dict(max_seconds=dt_ss, scans=n_ss))
@@ -979,7 +1053,7 @@ def main():
     # (the region's first block has nothing ahead of it: its PP call waits for its own copy + sort behind whatever the other helpers have
     # queued -- 20-25 ms once per helper, MODEST_BENCH_TRACE=1 -- so the region is twice the contract region: four to five blocks per helper)
     n_wi = max(2 * a.steps, STEADY_STEPS_PER_HELPER * n_pool) if helpers else a.steps
-    if True:
+    if a.full:
         if helpers:
             dt_wi, _ = timed_region(helpers, _split(n_wi, n_pool), ingest=True)
         else:
@@ -1001,7 +1075,7 @@ def main():
     # the same stage with nothing else on the GPU (the timed region has several scans in flight, so its
     # event pairs also see the other scans' kernels): informational, not the reported `achieved`
     iso_ms, iso_B, iso_block, real = None, 1, False, None
-    if rank == 0:
+    if rank == 0 and a.full:
         if helpers:
             helpers[0][1].send(("iso", None))
             iso = helpers[0][1].recv()[1]
@@ -1121,17 +1195,19 @@ def main():
     else:
         roofline = dict(roofline_best, note="the realistic-sharing measurement was not taken (--sharing best, or it failed: see roofline_realistic_error); "
                                             "this is the best-case figure")
+    if not a.full:   # (the roofline figures rest on the isolated PP measurements, taken with --full only)
+        roofline = roofline_best = roofline_real = None
     cpu_baseline = None
     parity = None
     cli = None
     # the CLI leg first: with the CPU baselines (and the joblib worker processes they leave behind) before it, the first CLI
     # phase came out 3-4x slower in two of about ten default runs; stand-alone runs of the same CLI never did
-    if rank == 0 and ws == 1 and a.cli_scans > 0 and not a.pp_only and not a.nusc:
+    if a.full and rank == 0 and ws == 1 and a.cli_scans > 0 and not a.pp_only and not a.nusc:
         try:
             cli = cli_bench(a, local)
         except Exception as e:
             cli = {"error": repr(e)}
-    if rank == 0 and ws == 1 and a.cpu_scans > 0:
+    if a.full and rank == 0 and ws == 1 and a.cpu_scans > 0:
         from oracle import labels as ol
         from oracle import mask as om
         from oracle import pp_score as opp
@@ -1242,7 +1318,8 @@ def main():
                        "ransac_trial_loops": "host" if os.environ.get("MODEST_RANSAC_HOST") else "device",
                        "runtime_env": {k: os.environ.get(k) for k in ("HSA_ENABLE_INTERRUPT", "HSA_ENABLE_IPC_MODE_LEGACY",
                                                                       "GPU_MAX_HW_QUEUES")},
-                       "parallelism": f"scan-sharded x{ws} (no data-path collective)"},
+                       "parallelism": f"scan-sharded x{ws} (no data-path collective)",
+                       "full": bool(a.full)},
             "roofline": roofline, "roofline_best_case": roofline_best,
             "roofline_realistic_error": (roofline_real if (roofline_real and "error" in roofline_real) else None),
             "cpu_baseline": cpu_baseline, "parity": parity, "cli": cli, "steady_state": steady,

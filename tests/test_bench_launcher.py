@@ -28,6 +28,47 @@ def test_launch_command_is_one_rank_per_gpu_on_localhost():
     assert os.path.basename(cmd[-7]) == "bench.py"
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_arrays_are_float_and_capped(tmp_path):
+    """--dump-outputs: what one step hands back, as float32 / float64 .npy files; over the cap a fixed, seeded sample of the points."""
+    import numpy as np
+    import torch
+    import bench
+    text = ("Dynamic -1 -1 -1.5708 100.0000 150.0000 200.0000 250.0000 1.5000 1.8000 4.2000 1.0000 1.6000 20.0000 0.0000\n"
+            "Dynamic -1 -1 0.1000 10.0000 15.0000 20.0000 25.0000 1.0000 0.5000 0.7000 -3.0000 1.2000 9.5000 0.2500")
+    lf = bench.label_fields(text)
+    assert lf.dtype == np.float64 and lf.shape == (2, bench.LABEL_FIELDS) and lf[0, 0] == -1 and lf[1, -1] == 0.25
+    assert bench.label_fields("").shape == (0, bench.LABEL_FIELDS)
+    n = 5000
+    H = torch.linspace(0, 1, n, dtype=torch.float32)
+    labels = np.arange(n, dtype=np.int64) % 7
+    rows = np.random.RandomState(1).rand(2, 8)
+    arrays = bench.step_arrays((H, labels, rows, text))
+    assert sorted(arrays) == ["boxes", "cluster_labels", "label_fields", "pp_score"]
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    assert arrays["pp_score"].dtype == np.float32 and np.array_equal(arrays["cluster_labels"], labels)
+    assert bench.step_arrays((H, None, None, None)).keys() == {"pp_score"}   # --pp-only
+    names = bench.write_outputs(str(tmp_path / "all"), arrays)
+    assert names == sorted(arrays)
+    assert np.array_equal(np.load(tmp_path / "all" / "pp_score.npy"), H.numpy())
+    cap = 30000   # bytes: fewer than the 5000 points' 60 000
+    bench.write_outputs(str(tmp_path / "s1"), arrays, cap=cap)
+    bench.write_outputs(str(tmp_path / "s2"), arrays, cap=cap)
+    files = sorted(p.name for p in (tmp_path / "s1").iterdir())
+    assert files == ["boxes.npy", "cluster_labels.npy", "label_fields.npy", "point_index.npy", "pp_score.npy"]
+    assert sum(np.load(tmp_path / "s1" / f).nbytes for f in files) <= cap
+    idx = np.load(tmp_path / "s1" / "point_index.npy").astype(np.int64)
+    assert len(idx) > 0 and np.array_equal(np.load(tmp_path / "s1" / "pp_score.npy"), H.numpy()[idx])
+    assert all(np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)) for f in files)
+
+
 def test_world_size_mismatch_fails_loudly():
     """Under a launcher that started the wrong number of ranks the bench refuses to run (round 1: it
     silently measured one GPU)."""

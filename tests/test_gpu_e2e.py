@@ -246,13 +246,13 @@ def test_library_stage_driver_equals_python_statement(gpu):
 
 
 def test_bench_contract_json_line(gpu):
-    """`python bench.py` prints exactly one JSON line with the driver's contract fields, the roofline
+    """`python bench.py --full` prints exactly one JSON line with the driver's contract fields, the roofline
     object of the PP stage and the cpu_baseline object (small sizes, two helper processes)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "2", "--procs", "2", "--scans", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "16", "--warmup", "2", "--procs", "2", "--scans", "2",
            "--cpu-scans", "1", "--cpu-best-effort", "2", "--cli-scans", "3", "--cli-workers", "2", "--n-live", "8000", "--traversals", "3",
            "--frames", "6"]   # (two CLI workers for three scans: six would only start interpreters)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
@@ -293,6 +293,59 @@ def test_bench_contract_json_line(gpu):
     assert d["parity"]["pp_counts_equal"] is True and d["parity"]["labels_equal"] is True
     assert d["parity"]["label_text_equal"] is True
     assert d["cli"]["label_files"] == 3 and d["cli"]["pp_scans_per_s"] > 0 and d["cli"]["mask_scans_per_s"] > 0
+
+
+def test_bench_plain_run_and_dumped_outputs(gpu, tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and prints the contract fields alone (everything --full adds is
+    null); --dump-outputs writes the last timed step's outputs, the same in two runs with the same arguments, and they are
+    what the oracle computes for that scan."""
+    import json
+    import subprocess
+    import sys
+    import tempfile
+    from modest_amd import synth
+    from oracle import labels as ol
+    from oracle import mask as om
+    from oracle import pp_score as opp
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dirs = [], []
+    for rep in range(2):
+        dirs.append(str(tmp_path / f"out{rep}"))
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--procs", "2",
+               "--scans", "4", "--shard-scans", "4", "--n-live", "8000", "--traversals", "3", "--frames", "6", "--dump-outputs", dirs[-1]]
+        env = dict(os.environ, MODEST_MIN_STEPS_PER_HELPER="5")   # (10 steps: both helpers, 5 each)
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 10 and d["warmup"] == 2 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["ms_per_step"] * d["value"] - 1000.0) < 1e-6 * 1000.0
+    assert d["config"]["full"] is False and d["config"]["host_processes_per_gpu"] == 2
+    assert sum(d["config"]["pp_calls_in_timed_region"]["scans_per_call"]) == 10   # the steps the clock covered
+    for k in ("roofline", "roofline_best_case", "cpu_baseline", "parity", "cli", "steady_state", "value_with_ingest"):
+        assert d[k] is None, k
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["boxes.npy", "cluster_labels.npy", "label_fields.npy", "pp_score.npy"], names
+    got = {n[:-4]: np.load(os.path.join(dirs[0], n)) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(os.path.join(dirs[1], n))), n
+    # the last step of helper 1 (slot 1): its step n_warm + 4 = scan (n_warm + 4) mod 4 of its shard, RANSAC seeded by the step
+    import bench
+    n_warm = 4   # whole blocks of --pp-batch (clamped to the 4-scan shard) covering max(warmup, 2, 4)
+    step = n_warm + 5 - 1
+    sh = synth.make_shard(4, n_live=8000, n_trav=3, n_frames=6, seed=bench.scan_seed(0, 1, 0), x0=0.0)
+    live_xyz, hist = sh.stacked(step % 4)
+    Href, _ = opp.pp_score(live_xyz, hist, 0.3)
+    assert len(got["pp_score"]) == len(live_xyz) and np.max(np.abs(got["pp_score"].astype(np.float64) - Href)) <= 1e-6
+    with tempfile.TemporaryDirectory() as t:
+        open(os.path.join(t, "c.txt"), "w").write(synth.CALIB_TXT)
+        ocalib = ol.Calibration(os.path.join(t, "c.txt"))
+    ref = om.generate_mask_scan(sh.scans[step % 4].live_raw, got["pp_score"], ocalib, random_state=np.random.RandomState(step))
+    assert np.array_equal(got["cluster_labels"], ref["labels"])
+    assert np.array_equal(got["label_fields"], bench.label_fields(ol.gen_label_scan(ref["objs"], ocalib)[0]))
 
 
 def _pp_cli(tmp_path, golden_dir, tag, extra):

@@ -4,12 +4,12 @@ cd $GRAFT_REPO_ROOT
 F=gpurun_out/final; rm -rf $F; mkdir -p $F
 line() { grep '^{"metric"' | tail -1; }
 python bench.py --cpu-scans 0 --cli-scans 0 > /dev/null 2>&1   # warm the box (clocks, page cache)
-python bench.py 2>/dev/null | line > $F/bench_full.json
-python bench.py --cpu-scans 0 --cli-scans 0 --procs 1 --streams 1 2>/dev/null | line > $F/bench_full_1proc.json
-python bench.py --cpu-scans 0 --cli-scans 0 --procs 1 --streams 6 2>/dev/null | line > $F/bench_full_1proc_6threads.json
-python bench.py --steps 20 --warmup 5 --cpu-scans 0 --cli-scans 0 2>/dev/null | line > $F/bench_driver_steps20.json
-python bench.py --pp-only --cpu-scans 0 --cli-scans 0 2>/dev/null | line > $F/bench_pp_only.json
-python bench.py --pp-only --cpu-scans 0 --cli-scans 0 --procs 1 --streams 1 2>/dev/null | line > $F/bench_pp_only_1stream.json
+python bench.py --full 2>/dev/null | line > $F/bench_full.json
+python bench.py --full --cpu-scans 0 --cli-scans 0 --procs 1 --streams 1 2>/dev/null | line > $F/bench_full_1proc.json
+python bench.py --full --cpu-scans 0 --cli-scans 0 --procs 1 --streams 6 2>/dev/null | line > $F/bench_full_1proc_6threads.json
+python bench.py --full --steps 20 --warmup 5 --cpu-scans 0 --cli-scans 0 2>/dev/null | line > $F/bench_driver_steps20.json
+python bench.py --full --pp-only --cpu-scans 0 --cli-scans 0 2>/dev/null | line > $F/bench_pp_only.json
+python bench.py --full --pp-only --cpu-scans 0 --cli-scans 0 --procs 1 --streams 1 2>/dev/null | line > $F/bench_pp_only_1stream.json
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 # the default command: rank process + helper processes, one output set per process, merged
 rm -rf gpurun_out/prof_default

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -5
 python __graft_entry__.py --smoke 2>&1 | tail -1
-python bench.py 2>/dev/null | grep '^{"metric"' > gpurun_out/bench_full.json; cat gpurun_out/bench_full.json
+python bench.py --full 2>/dev/null | grep '^{"metric"'
 python bench.py --pp-only --cpu-scans 0 --procs 1 --streams 4 2>/dev/null | grep '^{"metric"' > gpurun_out/bench_pp.json; cat gpurun_out/bench_pp.json
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 rm -rf gpurun_out/prof_bench
