@@ -295,7 +295,7 @@ int modest_plane_candidates(modest_ctx *ctx, const float *pts_dev, int n,
  * is even).  Blocking; result written to *mad_host.                         */
 int modest_mad_threshold(modest_ctx *ctx, const float *cand_xyz_dev,
                          int n_cand, float *mad_host, void *stream);
-/* The same for up to four candidate sets in ONE launch (one workgroup each): a scan's two plane fits
+/* The same for `count` candidate sets, one workgroup each, up to 16 sets per launch: a scan's two plane fits
  * (generate_mask.py:55-56 and clustering_utils.py:126) take their thresholds from one call.
  * cand_xyz_dev / n_cand: host arrays of `count` device pointers / sizes (each >= 1); mad_host[count].
  * Blocking.                                                                 */

@@ -1258,20 +1258,24 @@ extern "C" int modest_mad_threshold(modest_ctx *ctx, const float *cand, int n_ca
 extern "C" int modest_mad_threshold_batch(modest_ctx *ctx, const float *const *cand, const int32_t *n_cand,
                                           int count, float *mad_host, void *stream_) {
     MODEST_REQUIRE(ctx != nullptr && cand != nullptr && n_cand != nullptr && mad_host != nullptr, "NULL argument");
-    MODEST_REQUIRE(count >= 1 && count <= 4, "1..4 candidate sets per call");
+    MODEST_REQUIRE(count >= 1, "at least one candidate set");
+    for (int i = 0; i < count; ++i)
+        MODEST_REQUIRE(n_cand[i] >= 1 && cand[i] != nullptr, "every set needs at least one candidate");
     hipStream_t stream = as_stream(stream_);
     MODEST_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = modest_ctx_reserve_pinned(ctx, 64);
+    int rc = modest_ctx_reserve_pinned(ctx, std::max<size_t>(64, 8 * (size_t)count));
     if (rc) return rc;
-    MadArgs A{};
-    for (int i = 0; i < count; ++i) {
-        MODEST_REQUIRE(n_cand[i] >= 1 && cand[i] != nullptr, "every set needs at least one candidate");
-        A.cand[i] = cand[i];
-        A.n[i] = n_cand[i];
-        A.out[i] = reinterpret_cast<float *>(ctx->pinned) + 2 * i;
+    for (int i0 = 0; i0 < count; i0 += MAD_SETS) {   // a launch of up to MAD_SETS sets at a time
+        const int m = std::min(count - i0, MAD_SETS);
+        MadArgs A{};
+        for (int i = 0; i < m; ++i) {
+            A.cand[i] = cand[i0 + i];
+            A.n[i] = n_cand[i0 + i];
+            A.out[i] = reinterpret_cast<float *>(ctx->pinned) + 2 * (i0 + i);
+        }
+        mad_kernel<<<m, 1024, 0, stream>>>(A);
+        MODEST_HIP_CHECK(hipGetLastError());
     }
-    mad_kernel<<<count, 1024, 0, stream>>>(A);
-    MODEST_HIP_CHECK(hipGetLastError());
     MODEST_HIP_CHECK(hipStreamSynchronize(stream));
     for (int i = 0; i < count; ++i) mad_host[i] = reinterpret_cast<float *>(ctx->pinned)[2 * i + 1];
     return MODEST_OK;

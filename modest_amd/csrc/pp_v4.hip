@@ -1472,7 +1472,14 @@ static int pp_block_impl(modest_ctx *ctx, const modest_pp_block_frame *frames, i
     const size_t oCellOff = take((size_t)BT * 65 * 4), oSegRange = take(maxSegs * 8);
     const size_t oBaseSum = take((size_t)((BT + 1023) / 1024) * 8), oNeed = take((size_t)BT * 4), oNeedCand = take((size_t)BT * 4);
     const size_t oRecA = take((size_t)std::max<long long>(ntot, 1) * 16), oRecB = take((size_t)std::max<long long>(ntot, 1) * 16);
-    const size_t oDeal = take((size_t)(65 + 4 * ctx->num_cus + 64) * 4);   // b4_deal's tables
+    // join workgroups: one of 16 wavefronts per CU (MODEST_PP4_JWG: up to four), at least two per scan.  b4_deal's tables are
+    // [0, G] the first join workgroup of every scan and, from word 65 on, the scan of each of the NW join workgroups
+    const char *jw_env = getenv("MODEST_PP4_JWG");
+    const unsigned jwg = jw_env ? (unsigned)std::min(std::max(atoi(jw_env), 1), 4) : 1u;
+    const unsigned jx = std::max(jwg * (unsigned)ctx->num_cus / (unsigned)G, 2u);
+    const unsigned NW = jx * (unsigned)G;
+    const size_t dealWords = 65 + (size_t)NW;
+    const size_t oDeal = take(dealWords * 4);
     const size_t oCtrl = take(256);   // the block's cursors and crop ...
     const size_t oNeedMask = take((size_t)BT * 8);   // ... and, directly behind them, the tiles' scan masks: one memset clears both
     const size_t oCellCount = take((size_t)G * (NCpad + 4) * 4);   // contiguous over the scans: one memset
@@ -1626,10 +1633,7 @@ static int pp_block_impl(modest_ctx *ctx, const modest_pp_block_frame *frames, i
         b4_scan_finish<<<(unsigned)G, 1024, 0, stream>>>(B, dsc);
         b4_live_scatter<<<dim3(gN, (unsigned)G), 256, 0, stream>>>(B, dsc);
         b4_plan<<<dim3(std::max(8u, (unsigned)(8 * ctx->num_cus) / (unsigned)G), (unsigned)G), 256, 0, stream>>>(B, dsc);
-        const char *jw_env = getenv("MODEST_PP4_JWG");
-        unsigned jx = (unsigned)((jw_env ? std::min(atoi(jw_env), 4) : 1) * ctx->num_cus) / (unsigned)G;   // one workgroup of 16 wavefronts per CU
-        if (jx < 2) jx = 2;
-        const unsigned NW = jx * (unsigned)G;   // (<= 4 * num_cus + 64: the deal table's size)
+        MODEST_REQUIRE(G <= 64 && 65 + (size_t)NW <= dealWords, "b4_deal's table holds the join workgroups");
         b4_deal<<<1, 64, 0, stream>>>(B, dsc, NW);
         const char *dbg_env = getenv("MODEST_PP4_DBG");   // ablations: 1 no pair phase, 2 no four-cell tasks, 8 no one-cell tasks, 256 poses from memory, 512 phase times
         const char *tk_env = getenv("MODEST_PP4_TK");

@@ -185,7 +185,7 @@ def mad_threshold(cand: torch.Tensor, ctx: Optional[Context] = None) -> np.float
 
 
 def mad_threshold_batch(cands: Sequence[torch.Tensor], ctx: Optional[Context] = None) -> np.ndarray:
-    """MAD thresholds of up to four candidate sets from one launch (one workgroup per set)."""
+    """MAD thresholds of several candidate sets from one call (one workgroup per set, up to 16 sets per launch)."""
     lib = load()
     for t in cands:
         _dev(t, torch.float32, "cand")
