@@ -711,6 +711,55 @@ int modest_boxes_iou_bev_host(modest_ctx *ctx, const float *boxes_a_host,
                               int n_a, const float *boxes_b_host, int n_b,
                               float *out_host, void *stream);
 
+/* ---- ground planes for detector training (data_preprocessing/RANSAC.py:9-68) -------------
+ * For every frame of a batch: rect = project_velo_to_rect(rows[:, :3]) in float64 (the fma chain
+ * of modest_project_velo_to_rect, bit for bit), the candidates min_h < y < max_h, -10 < z < 70,
+ * -20 < x < 20 in row order (:32-38), and for n_cand >= 5 sklearn's RANSACRegressor() fitted to
+ * X = rect[:, [0, 2]], y = rect[:, 1] (:44) in float64: threshold median(|y - median(y)|) (numpy
+ * medians, exact), MT19937 triplets by tracking selection as sklearn consumes the generator,
+ * inliers |y - pred| <= thr, the sequential accept rule with _dynamic_max_trials, the refit of the
+ * consensus set (centred normal equations), and the plane (:45-52): w = (c0, -1, c1) / |.|,
+ * h = b / |.|.  Fewer than 5 candidates: w = (0, -1, 0), h = 1.65 (:40-43).
+ * rows_dev [dev] packed (R,4) float32 rows of all frames (16-byte aligned).
+ * frames_host [host, in/out] n_frames descriptors.  key/pos are numpy's RandomState state; on
+ * return they hold the generator advanced by the executed trials (untouched for a frame that is
+ * not fitted here).  chain = 1 (--global_seed: one RandomState consumed in frame order by the
+ * frames with >= 5 candidates): only frames_host[0].key/pos is read; frame k returns the state
+ * after it; the first frame with status MODEST_GP_HOST returns the state BEFORE it, and every
+ * later frame is MODEST_GP_HOST as well (the caller fits that frame and calls again on the rest).
+ * Status MODEST_GP_HOST (generator untouched): 5 <= n_cand <= 300 (sklearn samples by permutation
+ * below 301, utils/random.py), a degenerate triplet or consensus set, or a trial bound within 1e-7
+ * of an integer (host and device libm could round it to different sides).
+ * triplets_host [host, optional] (n_frames, max_trials, 3) int32: the drawn triplets.
+ * gpu_ms_host [host, optional]: HIP event time of the batch's kernels.
+ * Fixed launches per batch (selection + MAD, trials), one synchronise.  Blocking.               */
+#define MODEST_GP_FITTED 0
+#define MODEST_GP_DEFAULT 1        /* fewer than 5 candidates: the default plane */
+#define MODEST_GP_HOST 2           /* handed back to the host mirror (modest_amd/utils/ransac.py) */
+#define MODEST_GP_NO_CONSENSUS 3   /* sklearn raises ValueError */
+typedef struct modest_gp_frame {
+    int64_t row_offset;   /* first row of the frame in rows_dev */
+    int32_t n;            /* rows */
+    int32_t pos;          /* [in/out] RandomState.get_state()[2] */
+    double v2c[12];       /* Tr_velo_to_cam, row major 3x4 */
+    double r0[9];         /* R0_rect, row major 3x3 */
+    uint32_t key[624];    /* [in/out] RandomState.get_state()[1] */
+} modest_gp_frame;
+typedef struct modest_gp_params {
+    double min_h, max_h;       /* strict window on rect y */
+    double stop_probability;   /* 0.99 */
+    int32_t max_trials;        /* 100 (at most 4096) */
+    int32_t chain;             /* 0: every frame its own generator; 1: one generator across the frames */
+} modest_gp_params;
+typedef struct modest_gp_result {
+    double plane[4];           /* w0, w1, w2, h */
+    double median, mad;        /* median(y), residual threshold (n_cand > 300) */
+    int32_t n_cand, n_trials, n_inliers, status;
+} modest_gp_result;
+int modest_ground_planes(modest_ctx *ctx, const float *rows_dev, modest_gp_frame *frames_host, int n_frames,
+                         const modest_gp_params *params_host, modest_gp_result *results_host,
+                         int32_t *triplets_host, float *gpu_ms_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

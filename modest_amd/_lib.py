@@ -85,6 +85,7 @@ SIGNATURES = {
     "modest_pp_block_tables": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, C.c_int, VP, C.c_int32, VP, VP, VP, VP, VP]),
     "modest_host_read_files": (C.c_int64, [VP, C.c_int, VP, C.c_uint64, VP, C.c_int]),
     "modest_label_lines": (C.c_int, [VP, VP, C.c_int, VP, VP, VP, VP, VP, VP, C.c_int32, VP]),
+    "modest_ground_planes": (C.c_int, [VP, VP, VP, C.c_int, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

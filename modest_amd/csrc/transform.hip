@@ -8,6 +8,7 @@
 //     out = acc + T[r][3]
 // (the trailing 1*T[r][3] is an exact product, so that last fma is an add).
 #include "common.h"
+#include "rect.h"
 
 namespace {
 
@@ -101,34 +102,18 @@ __global__ __launch_bounds__(1024) void transform_filter_kernel(const float *__r
     }
 }
 
-// project_velo_to_rect (utils/kitti_util.py:327-329): rect = (R0 @ ([p,1] @ V2C^T)^T)^T in float64.
-// numpy hands both products to dgemm, whose k loop is one fused multiply-add chain per output
-// element (first product rounded, then fma per further term; the appended 1 makes the last term
-// of the first product an exact addend).
-struct RectMats {
-    double v[12];   // V2C, row major 3x4
-    double r[9];    // R0, row major 3x3
-};
+// project_velo_to_rect (utils/kitti_util.py:327-329) in float64: the dgemm fma chain of rect.h
+using modest::RectMats;
 __global__ __launch_bounds__(256) void velo_to_rect_kernel(const float *__restrict__ in, int n, int stride, RectMats M,
                                                            double *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *p = in + (size_t)i * stride;
-    const double x = p[0], y = p[1], z = p[2];
-    double ref[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double acc = __dmul_rn(x, M.v[4 * j]);
-        acc = fma(y, M.v[4 * j + 1], acc);
-        acc = fma(z, M.v[4 * j + 2], acc);
-        ref[j] = fma(1.0, M.v[4 * j + 3], acc);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double acc = __dmul_rn(M.r[3 * j], ref[0]);
-        acc = fma(M.r[3 * j + 1], ref[1], acc);
-        out[3 * (size_t)i + j] = fma(M.r[3 * j + 2], ref[2], acc);
-    }
+    double o[3];
+    modest::velo_to_rect(p[0], p[1], p[2], M, o);
+    out[3 * (size_t)i + 0] = o[0];
+    out[3 * (size_t)i + 1] = o[1];
+    out[3 * (size_t)i + 2] = o[2];
 }
 
 // the same for up to RECT_SETS scans in one launch (the box tail of a chain of scans): the scan is blockIdx.y
@@ -143,22 +128,12 @@ __global__ __launch_bounds__(256) void velo_to_rect_sets_kernel(RectSets S, Rect
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S.n[s]) return;
     const float *p = S.in[s] + (size_t)i * S.stride[s];
-    const double x = p[0], y = p[1], z = p[2];
-    double ref[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double acc = __dmul_rn(x, M.v[4 * j]);
-        acc = fma(y, M.v[4 * j + 1], acc);
-        acc = fma(z, M.v[4 * j + 2], acc);
-        ref[j] = fma(1.0, M.v[4 * j + 3], acc);
-    }
+    double o[3];
+    modest::velo_to_rect(p[0], p[1], p[2], M, o);
     double *out = S.out[s];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double acc = __dmul_rn(M.r[3 * j], ref[0]);
-        acc = fma(M.r[3 * j + 1], ref[1], acc);
-        out[3 * (size_t)i + j] = fma(M.r[3 * j + 2], ref[2], acc);
-    }
+    out[3 * (size_t)i + 0] = o[0];
+    out[3 * (size_t)i + 1] = o[1];
+    out[3 * (size_t)i + 2] = o[2];
 }
 
 }  // namespace

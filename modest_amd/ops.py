@@ -880,3 +880,40 @@ def nms(boxes: torch.Tensor, thresh: float, rotated: bool = True, ctx: Optional[
     fn = lib.modest_nms_bev if rotated else lib.modest_nms_normal
     check(fn(c.handle, boxes.data_ptr(), n, float(thresh), _np_ptr(keep), C.byref(num), _stream()), "modest_nms")
     return keep[: num.value]
+
+
+# --------------------------------------------------------------------------- ground planes (RANSAC.py)
+# numpy images of modest_gp_frame / modest_gp_params / modest_gp_result (include/modest_hip.h)
+GP_FRAME = np.dtype([("row_offset", "<i8"), ("n", "<i4"), ("pos", "<i4"), ("v2c", "<f8", (12,)), ("r0", "<f8", (9,)),
+                     ("key", "<u4", (624,))])
+GP_PARAMS = np.dtype([("min_h", "<f8"), ("max_h", "<f8"), ("stop_probability", "<f8"), ("max_trials", "<i4"),
+                      ("chain", "<i4")])
+GP_RESULT = np.dtype([("plane", "<f8", (4,)), ("median", "<f8"), ("mad", "<f8"), ("n_cand", "<i4"), ("n_trials", "<i4"),
+                      ("n_inliers", "<i4"), ("status", "<i4")])
+GP_FITTED, GP_DEFAULT, GP_HOST, GP_NO_CONSENSUS = 0, 1, 2, 3
+assert GP_FRAME.itemsize == 2680 and GP_PARAMS.itemsize == 32 and GP_RESULT.itemsize == 64
+
+
+def ground_planes(rows: torch.Tensor, frames: np.ndarray, min_h: float, max_h: float, chain: bool = False,
+                  max_trials: int = 100, stop_probability: float = 0.99, return_triplets: bool = False,
+                  ctx: Optional[Context] = None):
+    """RANSAC.py's fit of a batch of frames (modest_ground_planes).  rows: packed (R,4) float32 device rows;
+    frames: GP_FRAME array (row offset, n, calibration, generator), updated in place with the advanced generators.
+    Returns (GP_RESULT array, GPU milliseconds of the batch, triplets (F, max_trials, 3) int32 or None)."""
+    lib = load()
+    _dev(rows, torch.float32, "rows")
+    assert rows.ndim == 2 and rows.shape[1] == 4
+    assert frames.dtype == GP_FRAME and frames.flags.c_contiguous
+    if len(frames):
+        assert int((frames["row_offset"] + frames["n"]).max()) <= rows.shape[0]
+    P = np.zeros((), dtype=GP_PARAMS)
+    P["min_h"], P["max_h"], P["stop_probability"] = min_h, max_h, stop_probability
+    P["max_trials"], P["chain"] = max_trials, int(bool(chain))
+    res = np.zeros(len(frames), dtype=GP_RESULT)
+    trip = np.full((len(frames), max_trials, 3), -1, dtype=np.int32) if return_triplets else None
+    ms = C.c_float(0.0)
+    c = _ctx(ctx, rows)
+    check(lib.modest_ground_planes(c.handle, rows.data_ptr(), _np_ptr(frames), len(frames), _np_ptr(P), _np_ptr(res),
+                                   _np_ptr(trip) if trip is not None else None, C.byref(ms), _stream()),
+          "modest_ground_planes")
+    return res, float(ms.value), trip

@@ -511,3 +511,32 @@ def write_kitti_tree(root: str, meta: str, n_seq: int = 3, n_frames: int = 12, n
     with open(paths["idx_list"], "w") as fh:
         fh.write("\n".join(f"{track[0][o]:06d}" for o in origins))
     return paths
+
+
+# ---- full-size frames for the ground planes (modest_amd.ground_planes) -------------------------------------------------
+def ground_calib_txt(k: int) -> str:
+    """one of three KITTI calib texts: camera height and a small R0_rect rotation differ"""
+    ty = (-0.3, -0.1, -0.5)[k % 3]
+    a = np.radians((0.0, 0.4, -0.6)[k % 3])
+    r0 = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+    return CALIB_TXT.replace("R0_rect: 1 0 0 0 1 0 0 0 1", "R0_rect: " + " ".join(repr(float(v)) for v in r0.ravel())) \
+                    .replace("0 0 -1 -0.3 1 0 0 -0.5", f"0 0 -1 {ty} 1 0 0 -0.5")
+
+
+def ground_frame(rng: np.random.Generator, n: int, height: float = 2.1, tilt=(0.003, -0.002), clutter: float = 0.3) -> np.ndarray:
+    """(n,4) float32 velodyne rows of a Lyft-shaped frame: a tilted ground plane z = -height + tilt . (x, y) with 2 cm
+    noise inside 70 m ahead / 20 m sideways, a `clutter` share of points at random heights around it (objects, kerbs),
+    and the rest beyond the fitting window (behind, far to the side, overhead)."""
+    n_g = int(n * 0.6)
+    n_c = int(n * clutter * 0.6)
+    n_o = max(n - n_g - n_c, 0)
+    x = rng.uniform(-5.0, 75.0, n_g + n_c)
+    y = rng.uniform(-22.0, 22.0, n_g + n_c)
+    z = -height + tilt[0] * x + tilt[1] * y
+    z[:n_g] += rng.normal(0.0, 0.02, n_g)
+    z[n_g:] += rng.uniform(-0.6, 0.8, n_c)
+    xo = rng.uniform(-80.0, 80.0, n_o)
+    yo = rng.uniform(-80.0, 80.0, n_o)
+    zo = rng.uniform(-3.0, 6.0, n_o)
+    pts = np.stack([np.concatenate([x, xo]), np.concatenate([y, yo]), np.concatenate([z, zo]), rng.uniform(0, 1, n)], 1)
+    return pts[rng.permutation(n)].astype(np.float32)

@@ -252,3 +252,98 @@ def ransac_plane(cand: torch.Tensor, random_state=None, max_trials: int = 100, s
     res.triplets = np.concatenate(triplets) if triplets else np.zeros((0, 3), dtype=np.int64)
     res.best_model = best_model
     return res
+
+
+# ---- float64: the ground planes of data_preprocessing/RANSAC.py ------------------------------------------------------
+# RANSACRegressor().fit(X = rect[:, [0, 2]], y = rect[:, 1]) on float64 data, stated with the operations of
+# csrc/ground_planes.hip (trial planes, scoring, refit) so that the device and this mirror agree to the last bits where
+# it matters (inlier counts, trial counts) and to ~1e-15 elsewhere.  It fits the frames the device hands back (fewer than
+# 301 candidates: sklearn permutes there; degenerate triplets / consensus sets; a trial bound on a libm rounding
+# boundary) and is the CPU tests' reference.  sklearn is not imported.
+
+class GroundFit:
+    __slots__ = ("coef", "intercept", "n_trials", "n_inliers", "median", "threshold", "triplets")
+
+
+def triplet_plane64(x, z, y):
+    """(c0, c1, b) of y = c0 x + c1 z + b through three points (Python floats), or None when they are collinear in
+    (x, z).  Centred 2x2 normal equations, the exact operation order of ground_planes.hip: triplet_plane."""
+    mx, mz, my = (x[0] + x[1] + x[2]) / 3.0, (z[0] + z[1] + z[2]) / 3.0, (y[0] + y[1] + y[2]) / 3.0
+    a0, a1, a2 = x[0] - mx, x[1] - mx, x[2] - mx
+    b0, b1, b2 = z[0] - mz, z[1] - mz, z[2] - mz
+    e0, e1, e2 = y[0] - my, y[1] - my, y[2] - my
+    sxx, szz, sxz = a0 * a0 + a1 * a1 + a2 * a2, b0 * b0 + b1 * b1 + b2 * b2, a0 * b0 + a1 * b1 + a2 * b2
+    sxy, szy = a0 * e0 + a1 * e1 + a2 * e2, b0 * e0 + b1 * e1 + b2 * e2
+    det = sxx * szz - sxz * sxz
+    if not abs(det) > 1e-12 * max(sxx * szz, 1e-300):
+        return None
+    c0 = (sxy * szz - szy * sxz) / det
+    c1 = (szy * sxx - sxy * sxz) / det
+    return c0, c1, my - c0 * mx - c1 * mz
+
+
+def _lstsq_plane(X, y):
+    """LinearRegression's minimum-norm fit (centred lstsq) for the degenerate sets"""
+    xm, ym = X.mean(axis=0), y.mean()
+    coef = np.linalg.lstsq(X - xm, y - ym, rcond=None)[0]
+    return float(coef[0]), float(coef[1]), float(ym - xm @ coef)
+
+
+def ransac_plane64(X: np.ndarray, y: np.ndarray, random_state=None, max_trials: int = 100,
+                   stop_probability: float = 0.99) -> GroundFit:
+    """sklearn RANSACRegressor() defaults on float64 (n,2) X and (n,) y: threshold median(|y - median(y)|), triplets by
+    sample_without_replacement from `random_state` (advanced by the executed trials only), inliers |y - X @ coef - b| <=
+    thr, the sequential accept rule with the dynamic trial bound, the refit of the best consensus set."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    n = int(y.shape[0])
+    if n < 3:
+        raise ValueError("`min_samples` may not be larger than number of samples: n_samples = %d." % n)
+    rs = check_random_state(random_state)
+    med = np.median(y)
+    thr = np.median(np.abs(y - med))
+    n_best, score_best, best, mask_best = 1, -np.inf, None, None
+    n_trials, limit = 0, max_trials
+    trips = []
+    while n_trials < limit:
+        n_trials += 1
+        t = [int(v) for v in sample_without_replacement(n, 3, random_state=rs)]
+        trips.append(t)
+        m = triplet_plane64(X[t, 0].tolist(), X[t, 1].tolist(), y[t].tolist())
+        if m is None:
+            m = _lstsq_plane(X[t], y[t])
+        r = y - (X @ np.array(m[:2]) + m[2])
+        inl = np.abs(r) <= thr
+        nk = int(inl.sum())
+        if nk < n_best:
+            continue
+        yi = y[inl]
+        score = r2_from_sums(nk, float(np.sum(r[inl] ** 2)), float(yi.sum()), float(np.sum(yi * yi)))
+        if nk == n_best and score < score_best:
+            continue
+        n_best, score_best, best, mask_best = nk, score, m, inl
+        limit = min(limit, dynamic_max_trials(n_best, n, 3, stop_probability))
+    if best is None:
+        raise ValueError("RANSAC could not find a valid consensus set. All `max_trials` iterations were "
+                         "skipped because each randomly chosen sub-sample failed the passing criteria.")
+    Xi, yi = X[mask_best], y[mask_best]
+    cnt = float(Xi.shape[0])
+    mx, mz, my = Xi[:, 0].sum() / cnt, Xi[:, 1].sum() / cnt, yi.sum() / cnt
+    a, b, e = Xi[:, 0] - mx, Xi[:, 1] - mz, yi - my
+    sxx, sxz, szz, sxy, szy = (a * a).sum(), (a * b).sum(), (b * b).sum(), (a * e).sum(), (b * e).sum()
+    det = sxx * szz - sxz * sxz
+    if cnt >= 3 and abs(det) > 1e-12 * max(sxx * szz, 1e-300):
+        c0 = (sxy * szz - szy * sxz) / det
+        c1 = (szy * sxx - sxy * sxz) / det
+        icpt = my - c0 * mx - c1 * mz
+    else:
+        c0, c1, icpt = _lstsq_plane(Xi, yi)
+    res = GroundFit()
+    res.coef = np.array([c0, c1], dtype=np.float64)
+    res.intercept = float(icpt)
+    res.n_trials = n_trials
+    res.n_inliers = int(mask_best.sum())
+    res.median = float(med)
+    res.threshold = float(thr)
+    res.triplets = np.asarray(trips, dtype=np.int64).reshape(-1, 3)
+    return res
