@@ -760,6 +760,61 @@ int modest_ground_planes(modest_ctx *ctx, const float *rows_dev, modest_gp_frame
                          const modest_gp_params *params_host, modest_gp_result *results_host,
                          int32_t *triplets_host, float *gpu_ms_host, void *stream);
 
+/* ---- KITTI-style AP evaluation (kitti_object_eval_python/eval.py; csrc/kitti_eval.hip) ----
+ * A set of frames, each with nd detections and ng ground-truth boxes.  Boxes are float64 camera boxes
+ * (x, y, z, l, h, w, ry) in rows of 7, image boxes rows of 4; frame f's dt x gt block of overlaps is stored dt-major
+ * at pair_off (overlaps[j, i] of eval.py). */
+typedef struct {
+    int64_t dt_off, gt_off, pair_off;   /* first detection / gt box / pair of the frame in the set */
+    int32_t nd, ng;
+} modest_eval_frame;
+
+/* One configuration: a row of the ignore-flag tables (class x difficulty or range bucket) and a min overlap. */
+typedef struct {
+    int32_t flagset, pad;
+    double min_overlap;
+    int64_t num_valid_gt;               /* gt boxes with ignored_gt == 0 in this row (get_thresholds' num_gt) */
+} modest_eval_config;
+
+/* Device pointers of one statistics run (one metric, n_cfg configurations). */
+typedef struct {
+    const modest_eval_frame *frames;    /* [n_frames] */
+    const modest_eval_config *cfg;      /* [n_cfg] */
+    const double *dt_score;             /* [n_dt] */
+    const double *dt_bbox, *gt_bbox;    /* [n][4] image boxes: metric 0 (DontCare pass) */
+    const int8_t *gt_ign, *dt_ign;      /* [flagsets][n_gt] ignored_gt, [flagsets][n_dt] ignored_det (-1 / 0 / 1) */
+    const uint8_t *gt_dc;               /* [flagsets][n_gt] DontCare boxes of the row, or NULL */
+    const double *pair_sim;             /* (1 + cos(gt alpha - dt alpha)) / 2 per pair (aos, metric 0), or NULL */
+    double *tp_scores;                  /* [n_cfg][n_gt] pass A: score of the detection matched to each tp gt
+                                           (other slots keep the caller's fill value) */
+    int32_t *tp_count;                  /* [n_cfg] pass A: tp count (zeroed by the caller) */
+    double *thresholds;                 /* [n_cfg][64] */
+    int32_t *n_thresh;                  /* [n_cfg]: threshold count, negative when more than 64 */
+    int32_t *partial;                   /* [n_cfg][64][n_frames][4] pass B: tp, fp, fn per frame */
+    double *sim_partial;                /* [n_cfg][64][n_frames] pass B similarity per frame (NaN: none), or NULL */
+    int64_t n_gt, n_dt;
+    int32_t n_frames, n_cfg, metric, max_nd;   /* max_nd: the largest nd (sizes the LDS bitmaps) */
+} modest_eval_stats_args;
+
+/* limits: thresholds per configuration, detections per frame */
+int modest_eval_limits(int32_t *max_thresholds, int32_t *max_dt_per_frame);
+
+/* Overlaps of pairs [pair_base, pair_base + n_pairs) of the set (outputs indexed from 0).  bev_out: devRotateIoUEval
+ * (query = gt, box = dt) under crit_bev (-1 IoU, 0 / 1 over the gt / dt area, 2 area); d3_out: d3_box_overlap_kernel
+ * under crit_3d; img_out: image_box_overlap under crit_img.  Any output may be NULL.  Enqueue only. */
+int modest_eval_overlaps(const modest_eval_frame *frames_dev, int n_frames, int64_t pair_base, int64_t n_pairs,
+                         const double *dt_boxes, const double *gt_boxes, const double *dt_bbox, const double *gt_bbox,
+                         int crit_bev, int crit_3d, int crit_img, float *bev_out, float *d3_out, double *img_out,
+                         void *stream);
+
+/* compute_statistics_jit / get_thresholds / fused_compute_statistics, enqueue only.  stage 0: pass A over frames
+ * [frame_begin, frame_end) whose overlaps (float32, or float64 if overlaps_f64) start at pair pair_base; stage 1:
+ * thresholds from `sorted` (each row of tp_scores in descending order); stage 2: pass B over a frame range;
+ * stage 3: pr_out[n_cfg][64][4] = tp, fp, fn, similarity summed over all frames. */
+int modest_eval_statistics(int stage, const modest_eval_stats_args *args, int frame_begin, int frame_end,
+                           const void *overlaps, int overlaps_f64, int64_t pair_base, const double *sorted,
+                           double *pr_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

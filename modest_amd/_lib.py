@@ -86,6 +86,10 @@ SIGNATURES = {
     "modest_host_read_files": (C.c_int64, [VP, C.c_int, VP, C.c_uint64, VP, C.c_int]),
     "modest_label_lines": (C.c_int, [VP, VP, C.c_int, VP, VP, VP, VP, VP, VP, C.c_int32, VP]),
     "modest_ground_planes": (C.c_int, [VP, VP, VP, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_eval_limits": (C.c_int, [VP, VP]),
+    "modest_eval_overlaps": (C.c_int, [VP, C.c_int, C.c_int64, C.c_int64, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
+                                       VP, VP, VP, VP]),
+    "modest_eval_statistics": (C.c_int, [C.c_int, VP, C.c_int, C.c_int, VP, C.c_int, C.c_int64, VP, VP, VP]),
 }
 
 _lib = None

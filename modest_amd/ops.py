@@ -917,3 +917,45 @@ def ground_planes(rows: torch.Tensor, frames: np.ndarray, min_h: float, max_h: f
                                    _np_ptr(trip) if trip is not None else None, C.byref(ms), _stream()),
           "modest_ground_planes")
     return res, float(ms.value), trip
+
+
+# --------------------------------------------------------------------------- KITTI-style AP evaluation (kitti_eval.hip)
+def eval_overlaps(frames: torch.Tensor, n_frames: int, pair_base: int, n_pairs: int, dt_boxes: torch.Tensor,
+                  gt_boxes: torch.Tensor, dt_bbox: torch.Tensor, gt_bbox: torch.Tensor, crit=(-1, -1, -1),
+                  bev: Optional[torch.Tensor] = None, d3: Optional[torch.Tensor] = None,
+                  img: Optional[torch.Tensor] = None) -> None:
+    """modest_eval_overlaps: pairs [pair_base, pair_base + n_pairs) of a set of frames (EVAL_FRAME rows as bytes on the
+    device) into float32 bev / 3-D and float64 image-box outputs (enqueue only, on PyTorch's current stream)."""
+    lib = load()
+    for t, dt, nm in ((dt_boxes, torch.float64, "dt_boxes"), (gt_boxes, torch.float64, "gt_boxes"),
+                      (dt_bbox, torch.float64, "dt_bbox"), (gt_bbox, torch.float64, "gt_bbox")):
+        _dev(t, dt, nm)
+    for t, dt, nm in ((bev, torch.float32, "bev"), (d3, torch.float32, "d3"), (img, torch.float64, "img")):
+        if t is not None:
+            _dev(t, dt, nm)
+            assert t.numel() >= n_pairs, f"{nm} holds fewer than n_pairs values"
+    check(lib.modest_eval_overlaps(frames.data_ptr(), int(n_frames), int(pair_base), int(n_pairs), dt_boxes.data_ptr(),
+                                   gt_boxes.data_ptr(), dt_bbox.data_ptr(), gt_bbox.data_ptr(), int(crit[0]),
+                                   int(crit[1]), int(crit[2]), bev.data_ptr() if bev is not None else None,
+                                   d3.data_ptr() if d3 is not None else None, img.data_ptr() if img is not None else None,
+                                   _stream()), "modest_eval_overlaps")
+
+
+def eval_statistics(stage: int, args, frame_begin: int = 0, frame_end: int = 0,
+                    overlaps: Optional[torch.Tensor] = None, pair_base: int = 0,
+                    sorted_scores: Optional[torch.Tensor] = None, pr: Optional[torch.Tensor] = None) -> None:
+    """modest_eval_statistics: stage 0 pass A / 1 thresholds / 2 pass B / 3 sums (enqueue only).  args: the
+    kitti_eval._StatsArgs of the run (device pointers)."""
+    lib = load()
+    f64 = 0
+    if overlaps is not None:
+        assert overlaps.is_cuda and overlaps.dtype in (torch.float32, torch.float64)
+        f64 = int(overlaps.dtype == torch.float64)
+    if sorted_scores is not None:
+        _dev(sorted_scores, torch.float64, "sorted_scores")
+    if pr is not None:
+        _dev(pr, torch.float64, "pr")
+    check(lib.modest_eval_statistics(int(stage), C.byref(args), int(frame_begin), int(frame_end),
+                                     overlaps.data_ptr() if overlaps is not None else None, f64, int(pair_base),
+                                     sorted_scores.data_ptr() if sorted_scores is not None else None,
+                                     pr.data_ptr() if pr is not None else None, _stream()), "modest_eval_statistics")

@@ -540,3 +540,93 @@ def ground_frame(rng: np.random.Generator, n: int, height: float = 2.1, tilt=(0.
     zo = rng.uniform(-3.0, 6.0, n_o)
     pts = np.stack([np.concatenate([x, xo]), np.concatenate([y, yo]), np.concatenate([z, zo]), rng.uniform(0, 1, n)], 1)
     return pts[rng.permutation(n)].astype(np.float32)
+
+
+# --------------------------------------------------------------------------- KITTI-style evaluation sets
+EVAL_NAMES = ("Dynamic", "Car", "Van", "Pedestrian", "DontCare")
+
+
+def _eval_anno(rng, n, names, with_score):
+    a = {"name": np.array([names[k] for k in rng.integers(0, len(names), n)] if n else np.zeros(0, "<U1"))}
+    a["truncated"] = np.round(rng.choice([0.0, 0.1, 0.2, 0.4, 0.6], n), 2)
+    a["occluded"] = rng.integers(0, 4, n).astype(np.int64)
+    a["alpha"] = np.round(rng.uniform(-np.pi, np.pi, n), 2)
+    y1 = np.round(rng.uniform(100, 200, n), 2)
+    x1 = np.round(rng.uniform(0, 1000, n), 2)
+    a["bbox"] = np.stack([x1, y1, x1 + np.round(rng.uniform(10, 150, n), 2), y1 + np.round(rng.uniform(15, 120, n), 2)], 1)
+    a["dimensions"] = np.round(np.stack([rng.uniform(1.5, 5, n), rng.uniform(1.2, 2.5, n), rng.uniform(0.8, 2.2, n)], 1), 2)
+    a["location"] = np.round(np.stack([rng.uniform(-20, 20, n), rng.uniform(0.5, 2.5, n), rng.uniform(2, 90, n)], 1), 2)
+    a["rotation_y"] = np.round(rng.uniform(-np.pi, np.pi, n), 2)
+    if with_score:
+        a["score"] = np.round(rng.integers(1, 12, n) / 12.0, 4)     # quantised: ties
+    return a
+
+
+def _take(a, idx):
+    return {k: v[idx] for k, v in a.items()}
+
+
+def _jitter_det(rng, g, i, scale):
+    d = _take(g, [i])
+    d["location"] = np.round(d["location"] + rng.normal(0, scale, (1, 3)) * [1, 0.3, 1], 2)
+    d["dimensions"] = np.round(d["dimensions"] * (1 + rng.normal(0, scale / 4, (1, 3))), 2)
+    d["rotation_y"] = np.round(d["rotation_y"] + rng.normal(0, scale / 4, 1), 2)
+    d["bbox"] = np.round(d["bbox"] + rng.normal(0, 8 * scale, (1, 4)), 2)
+    d["alpha"] = np.round(d["alpha"] + rng.normal(0, 0.2, 1), 2)
+    return d
+
+
+def eval_frames(seed: int, n_frames: int = 120, max_gt: int = 8, max_dt: int = 7, names=EVAL_NAMES):
+    """(gt_annos, dt_annos) for AP evaluation: detections are jittered gt plus false positives, with misses,
+    quantised (tied) scores, frames without gt or without detections, and adversarial geometry (identical, nested,
+    edge-touching, 90-degree-rotated and far-apart boxes).  max_dt <= 7 keeps numpy's pairwise sum of a frame's
+    similarity equal to the sequential one."""
+    rng = np.random.default_rng(seed)
+    gts, dts = [], []
+    for f in range(n_frames):
+        ng = 0 if f % 17 == 3 else int(rng.integers(1, max_gt + 1))
+        g = _eval_anno(rng, ng, names, False)
+        parts = []
+        for i in range(ng):
+            if rng.random() < 0.75 and sum(len(p["name"]) for p in parts) < max_dt:
+                d = _jitter_det(rng, g, i, rng.choice([0.0, 0.05, 0.2, 0.6]) if f % 5 else 0.0)
+                if f % 7 == 0 and rng.random() < 0.5:       # nested: the same centre, shrunk
+                    d["dimensions"] = np.round(d["dimensions"] * 0.6, 2)
+                if f % 11 == 0 and rng.random() < 0.5:      # rotated by 90 degrees
+                    d["rotation_y"] = np.round(d["rotation_y"] + np.pi / 2, 2)
+                if f % 13 == 0 and rng.random() < 0.5:      # edge-touching: shifted by its own length along x
+                    d["location"] = d["location"] + [[float(d["dimensions"][0, 0]), 0, 0]]
+                    d["rotation_y"] = np.zeros(1)
+                parts.append(d)
+        n_fp = 0 if f % 19 == 5 else int(rng.integers(0, 3))
+        n_fp = min(n_fp, max_dt - sum(len(p["name"]) for p in parts))
+        if n_fp > 0:
+            fp = _eval_anno(rng, n_fp, names[:4], False)
+            if f % 23 == 1:                                   # far apart
+                fp["location"][:, 0] += 500
+            parts.append(fp)
+        if f % 19 == 5 or not parts:
+            d = _take(_eval_anno(rng, 0, names, False), [])
+        else:
+            d = {k: np.concatenate([p[k] for p in parts], 0) for k in parts[0]}
+            d["name"] = np.array([str(s) if s != "DontCare" else "Dynamic" for s in d["name"]])
+        d["score"] = np.round(rng.integers(1, 12, len(d["name"])) / 12.0, 4)
+        if f % 9 == 0 and len(d["name"]) > 1:               # exact duplicates of one detection
+            d = {k: np.concatenate([v, v[:1]], 0) for k, v in d.items()} if len(d["name"]) < max_dt else d
+        gts.append(g)
+        dts.append(d)
+    return gts, dts
+
+
+def label_text(anno) -> str:
+    """a label_2 file (%.4f) of an anno: dimensions written back in h w l order"""
+    lines = []
+    for k in range(len(anno["name"])):
+        l_, h, w = anno["dimensions"][k]
+        vals = [anno["truncated"][k], int(anno["occluded"][k]), anno["alpha"][k], *anno["bbox"][k], h, w, l_,
+                *anno["location"][k], anno["rotation_y"][k]]
+        s = "%s %.4f %d " % (anno["name"][k], vals[0], vals[1]) + " ".join("%.4f" % v for v in vals[2:])
+        if "score" in anno:
+            s += " %.4f" % anno["score"][k]
+        lines.append(s)
+    return "".join(x + "\n" for x in lines)
