@@ -182,3 +182,136 @@ def test_cli_on_label_tree_and_result_pkl(tmp_path):
         assert out.returncode == 0, out.stderr
         assert out.stdout.startswith(want + "\n")
         assert '"frames": 60' in out.stdout.splitlines()[-1]
+
+
+# ------------------------------------------------------------------------------------------------ past every capacity
+def _limit_frame(nd, seed=12):
+    """one frame of nd Car detections and 8 gt (6 Car, 2 DontCare).  Only detections at indices >= nd - 32 (the last
+    bitmap word) and three early duplicates overlap anything: the rest lie 1000 m and 3000 px away."""
+    from modest_amd import synth
+    rng = np.random.default_rng(seed)
+    g = synth._eval_anno(rng, 8, ("Car",), False)
+    g["name"] = np.array(["Car"] * 6 + ["DontCare"] * 2)
+    g["occluded"][:] = 0
+    g["truncated"][:] = 0.0
+    g["bbox"][:, 3] = g["bbox"][:, 1] + np.round(rng.uniform(45, 120, 8), 2)     # every Car easy
+    g["bbox"][6:] = [[1500, 150, 1600, 250], [1700, 150, 1800, 250]]              # apart from every Car
+    d = synth._eval_anno(rng, nd, ("Car",), True)
+    d["location"][:, 0] += 1000
+    d["bbox"][:, [0, 2]] += 3000
+    last = nd - 32
+    for k in range(6):                              # gt k: matched by detection last + k (and k < 3 by detection k)
+        for j in ([last + k, k] if k < 3 else [last + k]):
+            for key in ("location", "dimensions", "rotation_y", "bbox", "alpha"):
+                d[key][j] = g[key][k]
+        d["score"][last + k] = (0.95, 0.6, 0.3, 0.85, 0.45, 0.2)[k]
+    for k in range(6):                              # inside the DontCare boxes: taken by DontCare at metric 0
+        j = last + 10 + k
+        bb = g["bbox"][6 + k % 2]
+        d["bbox"][j] = [bb[0] + 1, bb[1] + 1, bb[2] - 1, bb[3] - 1]
+        d["score"][j] = 0.9
+    return g, d
+
+
+def _equal_to_restatement(es, frames, metric, rows, configs, compute_aos=False):
+    pr, nt = es.statistics(metric, rows, configs, compute_aos=compute_aos)
+    out = []
+    for c, (r, mo) in enumerate(configs):
+        cls, diff, rng = rows[r]
+        fl = seq.range_flags(frames, cls, rng) if rng else None
+        want, thr = seq.eval_config(frames, metric, cls, diff, mo, compute_aos=compute_aos, flags=fl)
+        assert nt[c] == len(thr), (c, rows[r], mo)
+        assert np.array_equal(pr[c, :nt[c], :3], want[:, :3]), (c, rows[r], mo)
+        if compute_aos:
+            assert np.array_equal(pr[c, :nt[c], 3], want[:, 3]), (c, rows[r], mo)
+        out.append(want)
+    return out
+
+
+def test_a_frame_at_the_detection_limit():
+    """8 192 detections: the last of the 256 bitmap words per lane, 64 KiB of dynamic LDS per workgroup"""
+    import ctypes
+    from modest_amd import _lib
+    from modest_amd import kitti_eval as ke
+    lim_t, lim_d = ctypes.c_int32(), ctypes.c_int32()
+    _lib.check(_lib.load().modest_eval_limits(ctypes.byref(lim_t), ctypes.byref(lim_d)), "modest_eval_limits")
+    nd = lim_d.value
+    assert nd == 8192
+    g, d = _limit_frame(nd)
+    es = ke.EvalSet([g], [d])
+    assert es.max_nd == nd
+    rows = [(0, 3, None), (0, 0, None)]
+    configs = [(0, 0.7), (0, 0.5), (1, 0.7)]
+    frames = [(g, d, ke.frame_overlaps([g], [d])[0][0])]
+    want = _equal_to_restatement(es, frames, 1, rows, configs)
+    assert max(w[:, 0].max() for w in want) >= 4      # gt 3-5 are matched only by detections in the last word
+    frames = [(g, d, ke.image_box_overlap(d["bbox"], g["bbox"]))]
+    want = _equal_to_restatement(es, frames, 0, rows, configs, compute_aos=True)
+    assert max(w[:, 0].max() for w in want) >= 4
+    # the DontCare boxes take the last word's detections: without them those would be false positives
+    _, ig, idt, dc = ke.clean_data(g, d, 0, 3)
+    ov = frames[0][2]
+    with_dc = seq.compute_statistics(ov, g["alpha"], d["alpha"], d["bbox"], d["score"], ig, idt, dc, 0, 0.5, 0.9, True)
+    without = seq.compute_statistics(ov, g["alpha"], d["alpha"], d["bbox"], d["score"], ig, idt, [], 0, 0.5, 0.9, True)
+    assert without[1] - with_dc[1] == 6
+    # one detection more is refused by name
+    g2, d2 = _limit_frame(nd + 1)
+    with pytest.raises(ValueError, match="8193 detections: at most 8192"):
+        ke.EvalSet([g2], [d2])
+
+
+def test_more_than_128_configurations_in_one_call():
+    """pass A runs 64 configurations per lane group (blockIdx.y) and ke_thresholds 64 per block: a third of each"""
+    from modest_amd import kitti_eval as ke
+    gt, dt = _stress_frames(13, 40)
+    es = ke.EvalSet(gt, dt)
+    rows = [(6, 3, None), (6, 0, None), (6, 1, None), (6, 2, None), (0, 0, None), (0, 3, None), (6, 3, (0, 30)),
+            (6, 3, (30, 50)), (6, 3, (50, 80))]
+    overlaps = np.round(np.linspace(0.05, 0.75, 15), 2)
+    configs = [(r, mo) for r in range(len(rows)) for mo in overlaps]
+    assert len(configs) > 128
+    frames = list(zip(gt, dt, [x[0] for x in ke.frame_overlaps(gt, dt)]))
+    want = _equal_to_restatement(es, frames, 1, rows, configs)
+    assert sum(int(w[:, 0].max(initial=0) > 0) for w in want[128:]) >= 3     # the third group finds TPs
+
+
+def test_more_than_64_configurations_through_the_public_api():
+    """seven classes and four range buckets plus the whole range: 7 x 5 x 2 = 70 configurations per metric"""
+    from modest_amd import kitti_eval as ke
+    from modest_amd import synth
+    names = ("Car", "Pedestrian", "Cyclist", "Van", "Person_sitting", "Truck", "Dynamic", "DontCare")
+    gt, dt = synth.eval_frames(14, n_frames=80, max_gt=10, max_dt=14, names=names)
+    ranges = (0, 20, 40, 60, 80)
+    classes = list(names[:7])
+    s_all, d_all = ke.get_range_eval_result(gt, dt, classes, ranges=ranges)
+    s_one = ""
+    for c in classes:
+        s, d = ke.get_range_eval_result(gt, dt, c, ranges=ranges)
+        assert len(d) == 4 * 5
+        for k in d:
+            assert float(d_all[k]) == float(d[k]), k
+        s_one += s
+    assert s_all == s_one
+    assert any(float(v) > 0 for k, v in d_all.items() if k.startswith("Dynamic"))
+
+
+def test_every_frame_its_own_batch(gold, monkeypatch):
+    """MODEST_EVAL_PAIR_BUDGET=1: the overlaps, pass A and pass B (with the aos similarity rebuilt per batch) run frame
+    by frame, and every number is the single-batch number"""
+    from modest_amd import kitti_eval as ke
+    gt, dt = _stress_frames(15, 120)
+    rows = [(0, 0, None), (0, 2, None), (1, 1, None), (6, 3, None)]
+    configs = [(r, mo) for r in range(len(rows)) for mo in (0.5, 0.7)]
+    one = ke.EvalSet(gt, dt)
+    assert len(one.batches) == 1
+    want = one.statistics(0, rows, configs, compute_aos=True)
+    want_off = ke.get_official_eval_result(gold["gt"], gold["dt"], "Car")
+    monkeypatch.setenv("MODEST_EVAL_PAIR_BUDGET", "1")
+    each = ke.EvalSet(gt, dt)
+    assert len(each.batches) >= sum(1 for g, d in zip(gt, dt) if len(g["name"]) * len(d["name"])) > 90
+    got = each.statistics(0, rows, configs, compute_aos=True)
+    assert np.array_equal(got[1], want[1])
+    assert np.array_equal(got[0], want[0], equal_nan=True)
+    assert (got[0][:, :, 3] > 0).any()
+    _same(ke.get_official_eval_result(gold["gt"], gold["dt"], "Car"), want_off)
+    _same(ke.get_official_eval_result(gold["gt"], gold["dt"], "Car"), gold["car"])
