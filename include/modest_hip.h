@@ -815,6 +815,59 @@ int modest_eval_statistics(int stage, const modest_eval_stats_args *args, int fr
                            const void *overlaps, int overlaps_f64, int64_t pair_base, const double *sorted,
                            double *pr_out, void *stream);
 
+/* ---- dataset infos + ground-truth database (OpenPCDet create_kitti_infos) ----------------
+ * csrc/kitti_infos.hip.  A batch of frames lies back to back in rows_dev as raw (n,4) float32 rows.
+ * Per box the calls return
+ *   hull_count   the rows inside the camera's field of view (all rows when fov_only = 0) that the float64
+ *                box test decides inside: num_points_in_gt of kitti_dataset.py:239-251 up to the undecided
+ *                rows (|margin| < tau), whose frame-local row numbers come back in und_idx (und_cap per box;
+ *                und_n counts all of them, und_n > und_cap means the list overflowed) for the host's Delaunay;
+ *   db_count     the members under check_pt_in_box3d_cpu (roiaware_pool3d.cpp:128-143, bit for bit) and, from
+ *                modest_infos_gather, those rows in file order with the float64 centre subtracted and rounded
+ *                once (kitti_dataset.py:290-292), box after box at box_base[box].
+ * The FOV flag is kitti_dataset.py:158-173 + calibration_kitti.py:64-84 in float32 (see the .hip header).
+ * Both calls only enqueue on `stream`; every buffer is the caller's.  frames / boxes are host tables (copied
+ * into tables_dev, modest_infos_table_bytes, 256-byte aligned); wcount_dev holds the per-chunk counts between
+ * the two calls (sum over frames of ceil(n / modest_infos_chunk_rows()) * box_count words).  A frame's boxes
+ * are processed in passes of pass_boxes <= MODEST_INFOS_MAX_PASS that share LDS.                      */
+#define MODEST_INFOS_MAX_PASS 256
+typedef struct modest_infos_frame {
+    int64_t row_offset;   /* first row of the frame in rows_dev */
+    int64_t cnt_offset;   /* first word of the frame in wcount_dev: running sum of chunks * box_count */
+    int32_t n;            /* rows */
+    int32_t box_begin;    /* first box of the frame in the box table (frames in order, no gaps) */
+    int32_t box_count;
+    int32_t height, width;   /* image_shape */
+    int32_t fov_only;     /* FOV_POINTS_ONLY: hull_count over the rows with the FOV flag only */
+    int32_t pad[2];
+    float m1[12];         /* V2C.T @ R0.T (float32 product of numpy), row major 4x3 */
+    float p2t[12];        /* P2.T, row major 4x3 */
+} modest_infos_frame;
+typedef struct modest_infos_box {
+    double b[7];          /* gt_boxes_lidar: x y z dx dy dz heading (float64) */
+    double cs[2];         /* cos(heading), sin(heading) in float64 */
+    double tau;           /* half width of the undecided band of the hull test, metres */
+    float bf[7];          /* the same seven rounded to float32 (what points_in_boxes_cpu receives) */
+    float cosa, sina;     /* the HOST libm's cosf(-bf[6]) / sinf(-bf[6]), the symbols the reference's host code binds to */
+    float reject;         /* max(|x-cx|, |y-cy|) above this: neither a member nor undecided */
+    float pad[2];
+} modest_infos_box;
+int modest_infos_chunk_rows(void);
+int64_t modest_infos_table_bytes(int n_frames, int n_boxes);
+/* fov_dev (optional): one byte per row of rows_dev, the FOV flag.  dense_dev (optional, zeroed by the caller):
+ * (n_boxes, dense_stride) int32, 1 where the database predicate holds (points_in_boxes_cpu's dense mask). */
+int modest_infos_count(const float *rows_dev, int64_t n_rows, const modest_infos_frame *frames_host, int n_frames,
+                       const modest_infos_box *boxes_host, int n_boxes, int pass_boxes, int und_cap,
+                       void *tables_dev, int64_t tables_bytes, int32_t *wcount_dev, int64_t wcount_words,
+                       int32_t *hull_count_dev, int32_t *und_n_dev, int32_t *und_idx_dev, int32_t *db_count_dev,
+                       uint8_t *fov_dev, int32_t *dense_dev, int64_t dense_stride, void *stream);
+/* after modest_infos_count on the same tables_dev / wcount_dev and a read-back of db_count: box_base is the exclusive
+ * sum of db_count over the batch's boxes (host copy for the bounds check, device copy for the kernel). */
+int modest_infos_gather(const float *rows_dev, int64_t n_rows, const modest_infos_frame *frames_host, int n_frames,
+                        int n_boxes, int pass_boxes, const void *tables_dev, const int32_t *wcount_dev,
+                        int64_t wcount_words, const int64_t *box_base_dev, const int32_t *db_count_host,
+                        const int64_t *box_base_host, float *out_rows_dev, int64_t out_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

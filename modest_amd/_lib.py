@@ -90,6 +90,12 @@ SIGNATURES = {
     "modest_eval_overlaps": (C.c_int, [VP, C.c_int, C.c_int64, C.c_int64, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
                                        VP, VP, VP, VP]),
     "modest_eval_statistics": (C.c_int, [C.c_int, VP, C.c_int, C.c_int, VP, C.c_int, C.c_int64, VP, VP, VP]),
+    "modest_infos_chunk_rows": (C.c_int, []),
+    "modest_infos_table_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "modest_infos_count": (C.c_int, [VP, C.c_int64, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64, VP, C.c_int64,
+                                     VP, VP, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_infos_gather": (C.c_int, [VP, C.c_int64, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int64, VP, VP, VP, VP,
+                                      C.c_int64, VP]),
 }
 
 _lib = None

@@ -959,3 +959,79 @@ def eval_statistics(stage: int, args, frame_begin: int = 0, frame_end: int = 0,
                                      overlaps.data_ptr() if overlaps is not None else None, f64, int(pair_base),
                                      sorted_scores.data_ptr() if sorted_scores is not None else None,
                                      pr.data_ptr() if pr is not None else None, _stream()), "modest_eval_statistics")
+
+
+# --------------------------------------------------------------------------- dataset infos + gt database (kitti_infos.hip)
+# numpy images of modest_infos_frame / modest_infos_box (include/modest_hip.h)
+INFOS_FRAME = np.dtype([("row_offset", "<i8"), ("cnt_offset", "<i8"), ("n", "<i4"), ("box_begin", "<i4"), ("box_count", "<i4"),
+                        ("height", "<i4"), ("width", "<i4"), ("fov_only", "<i4"), ("pad", "<i4", (2,)),
+                        ("m1", "<f4", (12,)), ("p2t", "<f4", (12,))])
+INFOS_BOX = np.dtype([("b", "<f8", (7,)), ("cs", "<f8", (2,)), ("tau", "<f8"), ("bf", "<f4", (7,)), ("cosa", "<f4"),
+                      ("sina", "<f4"), ("reject", "<f4"), ("pad", "<f4", (2,))])
+INFOS_MAX_PASS = 256
+assert INFOS_FRAME.itemsize == 144 and INFOS_BOX.itemsize == 128
+
+
+def infos_chunk_rows() -> int:
+    return int(load().modest_infos_chunk_rows())
+
+
+class InfosBatch:
+    """device state of one modest_infos_count call, kept for the read-back and for modest_infos_gather"""
+
+    def read(self):
+        """(hull_count, und_n, und_idx (n_boxes, und_cap), db_count) as numpy; synchronises"""
+        r = self.results.cpu().numpy()
+        nb, cap = self.n_boxes, self.und_cap
+        self.db_count = np.ascontiguousarray(r[2 * nb:3 * nb])
+        return r[:nb], r[nb:2 * nb], r[3 * nb:(3 + cap) * nb].reshape(nb, cap), self.db_count
+
+
+def infos_count(rows: torch.Tensor, n_rows: int, frames: np.ndarray, boxes: np.ndarray, wcount_words: Optional[int] = None,
+                pass_boxes: int = INFOS_MAX_PASS, und_cap: int = 32, want_fov: bool = False, dense_stride: int = 0) -> InfosBatch:
+    """modest_infos_count on PyTorch's current stream (enqueue only).  rows: packed (R,4) float32 device rows; frames /
+    boxes: INFOS_FRAME / INFOS_BOX host tables.  want_fov: also the FOV flag of every row (st.fov, uint8);
+    dense_stride > 0: also the dense (n_boxes, dense_stride) int32 database mask (st.dense)."""
+    lib = load()
+    _dev(rows, torch.float32, "rows")
+    assert rows.ndim == 2 and rows.shape[1] == 4 and 0 <= n_rows <= rows.shape[0]
+    assert frames.dtype == INFOS_FRAME and frames.flags.c_contiguous and boxes.dtype == INFOS_BOX and boxes.flags.c_contiguous
+    st = InfosBatch()
+    nf, nb = len(frames), len(boxes)
+    if wcount_words is None:
+        ch = infos_chunk_rows()
+        wcount_words = int(sum(-(-int(n) // ch) * int(c) for n, c in zip(frames["n"], frames["box_count"])))
+    st.rows, st.n_rows, st.frames, st.n_boxes, st.und_cap, st.pass_boxes = rows, int(n_rows), frames, nb, int(und_cap), int(pass_boxes)
+    st.wcount_words = int(wcount_words)
+    dev = rows.device
+    tb = int(lib.modest_infos_table_bytes(nf, nb))
+    st.tables = torch.empty((tb + 256,), dtype=torch.uint8, device=dev)
+    assert st.tables.data_ptr() % 256 == 0
+    st.wcount = torch.empty((max(st.wcount_words, 1),), dtype=torch.int32, device=dev)
+    st.results = torch.empty((max((3 + st.und_cap) * nb, 4),), dtype=torch.int32, device=dev)   # hull | und_n | db_count | und_idx
+    st.fov = torch.empty((max(st.n_rows, 1),), dtype=torch.uint8, device=dev) if want_fov else None
+    st.dense = torch.zeros((max(nb, 1), int(dense_stride)), dtype=torch.int32, device=dev) if dense_stride else None
+    base = st.results.data_ptr()
+    check(lib.modest_infos_count(rows.data_ptr(), st.n_rows, _np_ptr(frames), nf, _np_ptr(boxes) if nb else None, nb,
+                                 st.pass_boxes, st.und_cap, st.tables.data_ptr(), tb, st.wcount.data_ptr(), st.wcount_words,
+                                 base, base + 4 * nb, (base + 12 * nb) if st.und_cap else None, base + 8 * nb,
+                                 st.fov.data_ptr() if want_fov else None, st.dense.data_ptr() if dense_stride else None,
+                                 int(dense_stride), _stream()), "modest_infos_count")
+    return st
+
+
+def infos_gather(st: InfosBatch) -> np.ndarray:
+    """modest_infos_gather after st.read(): the database rows of the batch, box after box, as a (total, 4) float32 numpy
+    array (synchronises)."""
+    lib = load()
+    db_count = st.db_count
+    base = np.concatenate([[0], np.cumsum(db_count, dtype=np.int64)]).astype(np.int64)
+    total = int(base[-1])
+    dev = st.rows.device
+    out = torch.empty((max(total, 1), 4), dtype=torch.float32, device=dev)
+    base_dev = torch.from_numpy(base[:-1].copy() if st.n_boxes else np.zeros(1, dtype=np.int64)).to(dev)
+    check(lib.modest_infos_gather(st.rows.data_ptr(), st.n_rows, _np_ptr(st.frames), len(st.frames), st.n_boxes, st.pass_boxes,
+                                  st.tables.data_ptr(), st.wcount.data_ptr(), st.wcount_words, base_dev.data_ptr(),
+                                  _np_ptr(db_count) if st.n_boxes else _np_ptr(np.zeros(1, dtype=np.int32)),
+                                  _np_ptr(base), out.data_ptr(), total, _stream()), "modest_infos_gather")
+    return out[:total].cpu().numpy()

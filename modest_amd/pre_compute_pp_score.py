@@ -371,12 +371,17 @@ def relative_poses_block(fixed_l2es, fixed_egos, world_stacks, K, threads: int =
     return list(_POSE_POOL.map(lambda i: relative_poses(fixed_l2es[i], fixed_egos[i], world_stacks[i], K), range(n)))
 
 
-def save_npy_atomic(path, arr):
-    """np.save through a temporary file + os.replace: a killed rank never leaves a truncated .npy
-    that the skip-if-exists test would count as done."""
-    tmp = f"{path}.tmp{os.getpid()}.npy"
-    np.save(tmp, arr)
+def write_atomic(path, write, suffix=""):
+    """write(tmp) into a temporary file next to `path`, then os.replace: a killed rank never leaves a truncated file
+    that a skip-if-exists test (or a reader) would count as done."""
+    tmp = f"{path}.tmp{os.getpid()}{suffix}"
+    write(tmp)
     os.replace(tmp, path)
+
+
+def save_npy_atomic(path, arr):
+    """np.save through write_atomic"""
+    write_atomic(path, lambda tmp: np.save(tmp, arr), ".npy")
 
 
 def display_args(args):

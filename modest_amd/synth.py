@@ -630,3 +630,113 @@ def label_text(anno) -> str:
             s += " %.4f" % anno["score"][k]
         lines.append(s)
     return "".join(x + "\n" for x in lines)
+
+
+# ---- KITTI-format trees for modest_amd.kitti_infos (labels, calib, image headers, velodyne, ImageSets) --------------------
+# Everything below draws from RandomState.random_sample / permutation and uses +, -, *, / and sqrt only, so a tree is the
+# same bytes on every machine (no libm call decides a coordinate); tests/golden/kitti_infos.npz records digests of them.
+INFOS_IMAGE_SIZES = ((1224, 1024), (1242, 375), (1600, 900))   # (W, H)
+_INFOS_HEADINGS = (0.0, 1.5707963267948966, -1.5707963267948966, 3.141592653589793, -3.141592653589793)
+
+
+def infos_label_text(rs: np.random.RandomState, n_boxes: int, names=("Dynamic",), n_dontcare: int = 0, with_score: bool = False) -> str:
+    """n_boxes label lines (camera frame of CALIB_TXT) + n_dontcare DontCare lines.  Boxes lie 2..85 m ahead or up to 8 m
+    behind the camera, across and beyond the image's width; every third heading sits within 0.02 rad of 0, +-pi/2, +-pi;
+    every fourth box is a shifted copy of the one before it (overlap)."""
+    lines, prev = [], None
+    for k in range(n_boxes):
+        u = rs.random_sample(12)
+        if prev is not None and k % 4 == 3:
+            x, y, z, l, w, h, hd = prev
+            x, y, hd = x + 0.8 * (u[0] - 0.5), y + 0.8 * (u[1] - 0.5), hd + 0.3 * (u[2] - 0.5)
+        else:
+            x = -8.0 + 10.0 * u[0] if u[3] < 0.08 else 2.0 + 83.0 * u[0]
+            y = (u[1] - 0.5) * (1.5 * abs(x) + 4.0)
+            z = -1.8 + 1.2 * u[2]
+            l, w, h = 1.0 + 4.5 * u[4], 0.6 + 1.8 * u[5], 1.0 + 1.2 * u[6]
+            hd = _INFOS_HEADINGS[int(u[7] * 5) % 5] + 0.04 * (u[8] - 0.5) if k % 3 == 0 else 6.283 * (u[7] - 0.5)
+        prev = (x, y, z, l, w, h, hd)
+        ry = -hd - 1.5707963267948966
+        cam = (-y, -(z - h / 2) - 0.3, x - 0.5)
+        top = 100.0 + 400.0 * u[9]
+        hpx = (15.0, 30.0, 60.0)[int(u[10] * 3) % 3]
+        trunc, occ = (0.0, 0.2, 0.4, 0.7)[int(u[11] * 4) % 4], int(u[10] * 40) % 4
+        line = "%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f" % (
+            names[k % len(names)], trunc, occ, -10.0, 300.0 + 200.0 * u[9], top, 380.0 + 200.0 * u[9], top + hpx,
+            h, w, l, cam[0], cam[1], cam[2], ry)
+        if with_score:
+            line += " %.4f" % (0.05 + 0.9 * u[6])
+        lines.append(line)
+    for k in range(n_dontcare):
+        lines.append("DontCare -1 -1 -10 %.2f %.2f %.2f %.2f -1 -1 -1 -1000 -1000 -1000 -10" % (10.0 + k, 20.0, 60.0 + k, 50.0))
+    return "".join(x + "\n" for x in lines)
+
+
+def infos_points(seed: int, label_text: str, n_bg: int, per_box=(50, 2000)) -> np.ndarray:
+    """(n,4) float32 rows for a label file: n_bg background points over x -10..90, y -40..40, z -2.5..1.5 and, around
+    every labelled box, per_box[0]..per_box[1] points in the square that holds its footprint (so boxes hold tens to
+    thousands of points), shuffled."""
+    rs = np.random.RandomState(seed)
+    parts = [np.stack([-10.0 + 100.0 * rs.random_sample(n_bg), -40.0 + 80.0 * rs.random_sample(n_bg),
+                       -2.5 + 4.0 * rs.random_sample(n_bg)], axis=1)]
+    for line in label_text.splitlines():
+        v = line.split(" ")
+        if v[0] == "DontCare":
+            continue
+        h, w, l, cx, cy, cz = (float(t) for t in v[8:14])
+        x, y, z = cz + 0.5, -cx, -cy - 0.3 + h / 2
+        m = per_box[0] + int(rs.random_sample() * (per_box[1] - per_box[0]))
+        r = 0.5 * np.sqrt(l * l + w * w) + 0.3
+        u = rs.random_sample((m, 3))
+        parts.append(np.stack([x + r * (2 * u[:, 0] - 1), y + r * (2 * u[:, 1] - 1), z + (h / 2 + 0.2) * (2 * u[:, 2] - 1)], axis=1))
+    xyz = np.concatenate(parts)
+    refl = np.floor(rs.random_sample(len(xyz)) * 256.0) / 255.0
+    rows = np.concatenate([xyz, refl[:, None]], axis=1).astype(np.float32)
+    return np.ascontiguousarray(rows[rs.permutation(len(rows))])
+
+
+def infos_calib_text(k: int) -> str:
+    return CALIB_TXT if k % 2 == 0 else ground_calib_txt(k)
+
+
+def write_infos_scan(root: str, idx: str, rows: np.ndarray, label_text: str, calib_text: str, size) -> None:
+    """root/training/{velodyne,label_2,calib,image_2}/<idx>.*; the image is an empty 8-bit PNG of `size` = (W, H)"""
+    from PIL import Image
+    t = os.path.join(root, "training")
+    for d in ("velodyne", "label_2", "calib", "image_2"):
+        os.makedirs(os.path.join(t, d), exist_ok=True)
+    np.ascontiguousarray(rows, dtype=np.float32).tofile(os.path.join(t, "velodyne", idx + ".bin"))
+    with open(os.path.join(t, "label_2", idx + ".txt"), "w") as f:
+        f.write(label_text)
+    with open(os.path.join(t, "calib", idx + ".txt"), "w") as f:
+        f.write(calib_text)
+    Image.new("L", (int(size[0]), int(size[1]))).save(os.path.join(t, "image_2", idx + ".png"), compress_level=1)
+
+
+def write_infos_splits(root: str, train, val=None) -> None:
+    os.makedirs(os.path.join(root, "ImageSets"), exist_ok=True)
+    for name, ids in (("train", train), ("val", val)):
+        if ids is not None:
+            with open(os.path.join(root, "ImageSets", name + ".txt"), "w") as f:
+                f.write("".join(i + "\n" for i in ids))
+
+
+def write_infos_tree(root: str, seed: int, n_scans: int, n_pts=(60_000, 120_000), max_boxes: int = 12, big_every: int = 0,
+                     big_boxes: int = 300, per_box=(100, 400), val_every: int = 5) -> dict:
+    """A synthetic Lyft-shape tree for modest_amd.kitti_infos: n_scans scans of n_pts[0]..n_pts[1] points with 0..max_boxes
+    `Dynamic` boxes (every big_every-th scan: big_boxes of them, as a merged detector output brings); every
+    val_every-th scan goes to the val split.  Returns counters."""
+    rs = np.random.RandomState(seed)
+    train, val, boxes, points = [], [], 0, 0
+    for k in range(n_scans):
+        idx = "%06d" % k
+        nb = big_boxes if big_every and k % big_every == big_every - 1 else int(rs.random_sample() * (max_boxes + 1))
+        text = infos_label_text(rs, nb, with_score=(k % 2 == 1))
+        total = n_pts[0] + int(rs.random_sample() * (n_pts[1] - n_pts[0]))
+        rows = infos_points(seed * 100003 + k, text, max(total - nb * (per_box[0] + per_box[1]) // 2, 1000), per_box)
+        write_infos_scan(root, idx, rows, text, infos_calib_text(k), INFOS_IMAGE_SIZES[k % 3])
+        (val if val_every and k % val_every == val_every - 1 else train).append(idx)
+        boxes += nb
+        points += len(rows)
+    write_infos_splits(root, train, val if val_every else None)
+    return {"scans": n_scans, "train": len(train), "val": len(val), "boxes": boxes, "points": points}
