@@ -868,6 +868,52 @@ int modest_infos_gather(const float *rows_dev, int64_t n_rows, const modest_info
                         int64_t wcount_words, const int64_t *box_base_dev, const int32_t *db_count_host,
                         const int64_t *box_base_host, float *out_rows_dev, int64_t out_rows, void *stream);
 
+/* ---- a22 pointnet2_batch_cuda (pcdet/ops/pointnet2/pointnet2_batch/src/, bound at pointnet2_api.cpp:10-24) --------
+ * The nine launchers of the PointNet++ set-abstraction ops.  Every buffer [dev], float32 / int32, contiguous; enqueue
+ * only, no context.  Element offsets are 64-bit (the reference's int products overflow past 2^31 elements).  The
+ * arithmetic, the order of hits and the tie rules are the contract of DESIGN.md section 7d.  An index outside its row
+ * reads as 0 (forward) or is skipped (gradients); the reference reads or writes out of bounds.
+ *
+ * sampling_gpu.cu:100-216 furthest_point_sampling_kernel_launcher.  xyz (b,n,3), temp (b,n) (the caller fills it,
+ * 1e10 in the reference; values >= 0), idx (b,m).  idx[0] = 0; ties at the maximum of temp go to the point the
+ * reference's reduction tree picks (bs = min(1024, 2^floor(log2 n)): smallest bitreverse(k mod bs), then smallest k).
+ * On return temp holds the running minimum distances after m - 1 rounds; m = 1 writes idx[0] only.  n >= 1.        */
+int modest_pn2_furthest_point_sample(int b, int n, int m, const float *xyz_dev, float *temp_dev, int32_t *idx_dev,
+                                     void *stream);
+/* sampling_gpu.cu:15-31 gather_points_kernel_launcher_fast: points (b,c,n), idx (b,m) -> out (b,c,m).              */
+int modest_pn2_gather(int b, int c, int n, int m, const float *points_dev, const int32_t *idx_dev, float *out_dev,
+                      void *stream);
+/* sampling_gpu.cu:53-70 gather_points_grad_kernel_launcher_fast: grad_out (b,c,m), idx (b,m); ADDS into
+ * grad_points (b,c,n) (the caller zero-fills, as the reference's Python side does).                                */
+int modest_pn2_gather_grad(int b, int c, int n, int m, const float *grad_out_dev, const int32_t *idx_dev,
+                           float *grad_points_dev, void *stream);
+/* ball_query_gpu.cu:15-51 ball_query_kernel_launcher_fast: new_xyz (b,m,3), xyz (b,n,3) -> idx (b,m,nsample): the
+ * first nsample points with d2 < radius*radius (float32 product) in index order, short rows padded with the first
+ * hit, rows without a hit untouched (the caller zero-fills).                                                       */
+int modest_pn2_ball_query(int b, int n, int m, float radius, int nsample, const float *new_xyz_dev,
+                          const float *xyz_dev, int32_t *idx_dev, void *stream);
+/* group_points_gpu.cu:53-72 group_points_kernel_launcher_fast: points (b,c,n), idx (b,npoints,nsample) ->
+ * out (b,c,npoints,nsample).                                                                                       */
+int modest_pn2_group(int b, int c, int n, int npoints, int nsample, const float *points_dev, const int32_t *idx_dev,
+                     float *out_dev, void *stream);
+/* group_points_gpu.cu:14-31 group_points_grad_kernel_launcher_fast: grad_out (b,c,npoints,nsample); ADDS into
+ * grad_points (b,c,n).                                                                                             */
+int modest_pn2_group_grad(int b, int c, int n, int npoints, int nsample, const float *grad_out_dev,
+                          const int32_t *idx_dev, float *grad_points_dev, void *stream);
+/* interpolate_gpu.cu:16-59 three_nn_kernel_launcher_fast: unknown (b,n,3), known (b,m,3) -> dist2 (b,n,3) SQUARED
+ * distances ascending, idx (b,n,3); equal distances keep the lower index first; with m < 3 the unused slots hold
+ * inf / 0.                                                                                                         */
+int modest_pn2_three_nn(int b, int n, int m, const float *unknown_dev, const float *known_dev, float *dist2_dev,
+                        int32_t *idx_dev, void *stream);
+/* interpolate_gpu.cu:84-104 three_interpolate_kernel_launcher_fast: points (b,c,m), idx / weight (b,n,3) ->
+ * out (b,c,n) = (w0*p0 + w1*p1) + w2*p2.                                                                           */
+int modest_pn2_three_interpolate(int b, int c, int m, int n, const float *points_dev, const int32_t *idx_dev,
+                                 const float *weight_dev, float *out_dev, void *stream);
+/* interpolate_gpu.cu:127-149 three_interpolate_grad_kernel_launcher_fast: grad_out (b,c,n), idx / weight (b,n,3);
+ * ADDS grad_out * weight into grad_points (b,c,m).                                                                 */
+int modest_pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out_dev, const int32_t *idx_dev,
+                                      const float *weight_dev, float *grad_points_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

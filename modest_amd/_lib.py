@@ -96,6 +96,15 @@ SIGNATURES = {
                                      VP, VP, VP, VP, VP, VP, C.c_int64, VP]),
     "modest_infos_gather": (C.c_int, [VP, C.c_int64, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int64, VP, VP, VP, VP,
                                       C.c_int64, VP]),
+    "modest_pn2_furthest_point_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_gather_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_ball_query": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_group": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_group_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2_three_nn": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_pn2_three_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_pn2_three_interpolate_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

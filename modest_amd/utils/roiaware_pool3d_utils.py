@@ -2,7 +2,7 @@
 extension) on the GPU: the dense (num_boxes, num_points) int32 membership mask that ``create_groundtruth_database``, the
 ``gt_sampling`` augmentor and users' scripts ask for.  Same predicate, bit for bit, as
 ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-168; computed by csrc/kitti_infos.hip (``ops.infos_count``).
-``points_in_boxes_gpu``, the RoI pooling and the PointNet++ ops are not provided."""
+``points_in_boxes_gpu`` and the RoI pooling are not provided (the PointNet++ ops are in ``utils/pointnet2``)."""
 import numpy as np
 import torch
 
