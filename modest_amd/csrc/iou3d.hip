@@ -27,19 +27,19 @@ struct Pt {
     float x, y;
 };
 
-__device__ __forceinline__ float cross2(const Pt &a, const Pt &b) { return a.x * b.y - a.y * b.x; }
+__host__ __device__ __forceinline__ float cross2(const Pt &a, const Pt &b) { return a.x * b.y - a.y * b.x; }
 
-__device__ __forceinline__ float cross3(const Pt &p1, const Pt &p2, const Pt &p0) {
+__host__ __device__ __forceinline__ float cross3(const Pt &p1, const Pt &p2, const Pt &p0) {
     return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
 }
 
-__device__ __forceinline__ bool rect_cross(const Pt &p1, const Pt &p2, const Pt &q1, const Pt &q2) {
+__host__ __device__ __forceinline__ bool rect_cross(const Pt &p1, const Pt &p2, const Pt &q1, const Pt &q2) {
     return fminf(p1.x, p2.x) <= fmaxf(q1.x, q2.x) && fminf(q1.x, q2.x) <= fmaxf(p1.x, p2.x) &&
            fminf(p1.y, p2.y) <= fmaxf(q1.y, q2.y) && fminf(q1.y, q2.y) <= fmaxf(p1.y, p2.y);
 }
 
 // Point-in-rotated-box with the reference's 1e-2 margin; (c,s) = cos/sin(-heading).
-__device__ __forceinline__ bool in_box2d(const float *box, float c, float s, const Pt &p) {
+__host__ __device__ __forceinline__ bool in_box2d(const float *box, float c, float s, const Pt &p) {
     const float MARGIN = 1e-2f;
     const float cx = box[0], cy = box[1];
     const float rx = (p.x - cx) * c + (p.y - cy) * (-s);
@@ -47,7 +47,7 @@ __device__ __forceinline__ bool in_box2d(const float *box, float c, float s, con
     return fabsf(rx) < box[3] / 2 + MARGIN && fabsf(ry) < box[4] / 2 + MARGIN;
 }
 
-__device__ __forceinline__ bool seg_intersection(const Pt &p1, const Pt &p0, const Pt &q1,
+__host__ __device__ __forceinline__ bool seg_intersection(const Pt &p1, const Pt &p0, const Pt &q1,
                                                  const Pt &q0, Pt &ans) {
     if (!rect_cross(p0, p1, q0, q1)) return false;
     const float s1 = cross3(q0, p1, p0);
@@ -69,7 +69,7 @@ __device__ __forceinline__ bool seg_intersection(const Pt &p1, const Pt &p0, con
     return true;
 }
 
-__device__ __forceinline__ void rot_center(const Pt &ctr, float c, float s, Pt &p) {
+__host__ __device__ __forceinline__ void rot_center(const Pt &ctr, float c, float s, Pt &p) {
     const float nx = (p.x - ctr.x) * c + (p.y - ctr.y) * (-s) + ctr.x;
     const float ny = (p.x - ctr.x) * s + (p.y - ctr.y) * c + ctr.y;
     p.x = nx;
@@ -84,8 +84,18 @@ struct PolyLds {
     float x[POLY_MAX][NMS_TPB], y[POLY_MAX][NMS_TPB], ang[POLY_MAX][NMS_TPB];
 };
 
+// TIES: the kernels that are handed the host's cosf / sinf must equal the reference's CPU path bit for bit (objs_nms),
+// and that path sorts the vertices by glibc's atan2f, which is not correctly rounded and cannot be evaluated here.  Both
+// atan2f and atan2_f32 are within 1 ulp of the angle, so they order two vertices alike unless the sorted angles lie
+// closer than TIE_REL (8 ulp) of each other: such a pair is reported (unless the two vertices are the same point,
+// which any order serves) and its value recomputed on the host (host_iou_bev).  Measured on constructed degenerate
+// pairs (the same rectangle in another parametrisation, boxes turned by 1e-7, shared edges): 1 pair in 2 500; none among
+// random boxes or identical ones.
+constexpr float TIE_REL = 1e-6f;
+
 // ta / tb = (cos h, sin h, cos(-h), sin(-h)) of the two headings
-__device__ float box_overlap(const float *a, const float *b, const float4 ta, const float4 tb, PolyLds &L) {
+template <bool TIES = false>
+__device__ float box_overlap(const float *a, const float *b, const float4 ta, const float4 tb, PolyLds &L, bool *tie = nullptr) {
     const int ln = threadIdx.x & (NMS_TPB - 1);
     const float a_dxh = a[3] / 2, b_dxh = b[3] / 2, a_dyh = a[4] / 2, b_dyh = b[4] / 2;
     const float ax1 = a[0] - a_dxh, ay1 = a[1] - a_dyh, ax2 = a[0] + a_dxh, ay2 = a[1] + a_dyh;
@@ -151,6 +161,16 @@ __device__ float box_overlap(const float *a, const float *b, const float4 ta, co
                 L.ang[i + 1][ln] = a0;
             }
         }
+    if (TIES) {
+        bool t = false;
+        for (int k = 0; k + 1 < cnt; ++k) {
+            const float a0 = L.ang[k][ln], a1 = L.ang[k + 1][ln];
+            if (a1 - a0 <= fmaxf(fabsf(a0), fabsf(a1)) * TIE_REL &&
+                (L.x[k][ln] != L.x[k + 1][ln] || L.y[k][ln] != L.y[k + 1][ln]))
+                t = true;
+        }
+        *tie = t;
+    }
     float area = 0.f;
     const float x0 = cnt > 0 ? L.x[0][ln] : 0.f, y0 = cnt > 0 ? L.y[0][ln] : 0.f;
     for (int k = 0; k < cnt - 1; ++k) {
@@ -166,11 +186,70 @@ __device__ __forceinline__ float4 device_trig(float h) {
     return make_float4(modest::cos_f32(h), modest::sin_f32(h), modest::cos_f32(-h), modest::sin_f32(-h));
 }
 
-__device__ __forceinline__ float iou_bev(const float *a, const float *b, const float4 ta, const float4 tb, PolyLds &L) {
+template <bool TIES = false>
+__device__ __forceinline__ float iou_bev(const float *a, const float *b, const float4 ta, const float4 tb, PolyLds &L,
+                                         bool *tie = nullptr) {
     const float sa = a[3] * a[4];
     const float sb = b[3] * b[4];
-    const float so = box_overlap(a, b, ta, tb, L);
+    const float so = box_overlap<TIES>(a, b, ta, tb, L, tie);
     return so / fmaxf(sa + sb - so, IOU_EPS);
+}
+
+// The reference's CPU path itself (iou3d_cpu.cpp:128-229) for the pairs a host-trig kernel reports as ties: the same
+// float32 operations as box_overlap / iou_bev on rows of 11 floats (box + the host's trig), the vertices sorted by the
+// host's atan2f.
+float host_iou_bev(const float *a, const float *b) {
+    const float a_dxh = a[3] / 2, b_dxh = b[3] / 2, a_dyh = a[4] / 2, b_dyh = b[4] / 2;
+    const Pt ca{a[0], a[1]}, cb{b[0], b[1]};
+    Pt A[5] = {{a[0] - a_dxh, a[1] - a_dyh}, {a[0] + a_dxh, a[1] - a_dyh}, {a[0] + a_dxh, a[1] + a_dyh}, {a[0] - a_dxh, a[1] + a_dyh}, {0, 0}};
+    Pt B[5] = {{b[0] - b_dxh, b[1] - b_dyh}, {b[0] + b_dxh, b[1] - b_dyh}, {b[0] + b_dxh, b[1] + b_dyh}, {b[0] - b_dxh, b[1] + b_dyh}, {0, 0}};
+    for (int k = 0; k < 4; ++k) {
+        rot_center(ca, a[7], a[8], A[k]);
+        rot_center(cb, b[7], b[8], B[k]);
+    }
+    A[4] = A[0];
+    B[4] = B[0];
+    Pt poly[POLY_MAX], center{0.f, 0.f};
+    float ang[POLY_MAX];
+    int cnt = 0;
+    auto add = [&](const Pt &p) {
+        center.x = center.x + p.x;
+        center.y = center.y + p.y;
+        poly[cnt++] = p;
+    };
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            Pt x;
+            if (seg_intersection(A[i + 1], A[i], B[j + 1], B[j], x)) add(x);
+        }
+    for (int k = 0; k < 4; ++k) {
+        if (in_box2d(a, a[9], a[10], B[k])) add(B[k]);
+        if (in_box2d(b, b[9], b[10], A[k])) add(A[k]);
+    }
+    center.x /= cnt;
+    center.y /= cnt;
+    for (int i = 0; i < cnt; ++i) ang[i] = atan2f(poly[i].y - center.y, poly[i].x - center.x);
+    for (int j = 0; j < cnt - 1; ++j)
+        for (int i = 0; i < cnt - j - 1; ++i)
+            if (ang[i] > ang[i + 1]) {
+                std::swap(poly[i], poly[i + 1]);
+                std::swap(ang[i], ang[i + 1]);
+            }
+    float area = 0.f;
+    for (int k = 0; k < cnt - 1; ++k) {
+        const Pt u{poly[k].x - poly[0].x, poly[k].y - poly[0].y};
+        const Pt v{poly[k + 1].x - poly[0].x, poly[k + 1].y - poly[0].y};
+        area += cross2(u, v);
+    }
+    const float so = fabsf(area) / 2.0f;
+    return so / fmaxf(a[3] * a[4] + b[3] * b[4] - so, IOU_EPS);
+}
+
+// replace the reported pairs of an (na, nb) matrix by the host's value
+void host_resolve_ties(const float *A, int na, const float *B, int nb, float *out, const unsigned char *ties) {
+    const size_t total = (size_t)na * nb;
+    for (size_t id = 0; id < total; ++id)
+        if (ties[id]) out[id] = host_iou_bev(A + (id / nb) * 11, B + (id % nb) * 11);
 }
 
 __device__ __forceinline__ float iou_normal(const float *a, const float *b) {
@@ -188,7 +267,8 @@ __device__ __forceinline__ float iou_normal(const float *a, const float *b) {
 // SURVEY H6, so the label path uses the very cosf / sinf the reference's CPU path calls).
 template <bool IOU, bool HOSTTRIG>
 __device__ __forceinline__ void pair_kernel_body(const float *__restrict__ A, int na, const float *__restrict__ B, int nb,
-                                                 float *__restrict__ out, const unsigned bx) {
+                                                 float *__restrict__ out, unsigned char *__restrict__ ties, const unsigned bx) {
+    static_assert(IOU || !HOSTTRIG, "the host-trig kernels compute IoU only (host_iou_bev resolves their ties)");
     __shared__ PolyLds L;
     const long long id = (long long)bx * blockDim.x + threadIdx.x;
     if (id >= (long long)na * nb) return;
@@ -209,25 +289,32 @@ __device__ __forceinline__ void pair_kernel_body(const float *__restrict__ A, in
         ta = device_trig(a[6]);
         tb = device_trig(b[6]);
     }
-    out[id] = IOU ? iou_bev(a, b, ta, tb, L) : box_overlap(a, b, ta, tb, L);
+    if (HOSTTRIG) {   // IoU only: with the pair's tie report (box_overlap)
+        bool tie;
+        out[id] = iou_bev<true>(a, b, ta, tb, L, &tie);
+        ties[id] = tie ? 1 : 0;
+    } else {
+        out[id] = IOU ? iou_bev(a, b, ta, tb, L) : box_overlap(a, b, ta, tb, L);
+    }
 }
 template <bool IOU, bool HOSTTRIG>
 __global__ __launch_bounds__(NMS_TPB) void pair_kernel(const float *__restrict__ A, int na,
                                                        const float *__restrict__ B, int nb,
-                                                       float *__restrict__ out) {
-    pair_kernel_body<IOU, HOSTTRIG>(A, na, B, nb, out, blockIdx.x);
+                                                       float *__restrict__ out, unsigned char *__restrict__ ties) {
+    pair_kernel_body<IOU, HOSTTRIG>(A, na, B, nb, out, ties, blockIdx.x);
 }
 
 // the self-IoU matrices of several box sets in one launch (the label stage of a chain of scans): set = blockIdx.y
 struct PairSet {
     const float *boxes;   // rows of 11 floats (box + host trig)
     float *out;           // (n, n)
+    unsigned char *ties;  // (n, n): pairs to recompute on the host (box_overlap<TIES>)
     int n, pad;
 };
 __global__ __launch_bounds__(NMS_TPB) void pair_sets_kernel(const PairSet *__restrict__ sets) {
     const PairSet S = sets[blockIdx.y];
     if ((long long)blockIdx.x * NMS_TPB >= (long long)S.n * S.n) return;
-    pair_kernel_body<true, true>(S.boxes, S.n, S.boxes, S.n, S.out, blockIdx.x);
+    pair_kernel_body<true, true>(S.boxes, S.n, S.boxes, S.n, S.out, S.ties, blockIdx.x);
 }
 
 // ---- NMS over score-sorted boxes (semantics: src/iou3d_nms.cpp:90-136, nms_gpu / nms_normal_gpu) ----
@@ -287,9 +374,9 @@ int pair_launch(bool iou, const float *a, int na, const float *b, int nb, float 
     const long long total = (long long)na * nb;
     const int blocks = (int)((total + NMS_TPB - 1) / NMS_TPB);
     if (iou)
-        pair_kernel<true, false><<<blocks, NMS_TPB, 0, as_stream(stream)>>>(a, na, b, nb, out);
+        pair_kernel<true, false><<<blocks, NMS_TPB, 0, as_stream(stream)>>>(a, na, b, nb, out, nullptr);
     else
-        pair_kernel<false, false><<<blocks, NMS_TPB, 0, as_stream(stream)>>>(a, na, b, nb, out);
+        pair_kernel<false, false><<<blocks, NMS_TPB, 0, as_stream(stream)>>>(a, na, b, nb, out, nullptr);
     MODEST_HIP_CHECK(hipGetLastError());
     return MODEST_OK;
 }
@@ -379,7 +466,7 @@ int modest_boxes_self_iou_bev_host_batch(modest_ctx *ctx, const float *const *bo
     long long maxPairs = 0;
     for (int s = 0; s < B; ++s) {
         MODEST_REQUIRE(n[s] >= 0, "negative box count");
-        need += arena_sz((size_t)n[s] * 44) + arena_sz((size_t)n[s] * n[s] * 4);
+        need += arena_sz((size_t)n[s] * 44) + arena_sz((size_t)n[s] * n[s] * 4) + arena_sz((size_t)n[s] * n[s]);
         maxPairs = std::max(maxPairs, (long long)n[s] * n[s]);
     }
     if (maxPairs == 0) return MODEST_OK;
@@ -393,6 +480,8 @@ int modest_boxes_self_iou_bev_host_batch(modest_ctx *ctx, const float *const *bo
         off += arena_sz((size_t)n[s] * 44);
         float *po = reinterpret_cast<float *>(ctx->pinned + off);
         off += arena_sz((size_t)n[s] * n[s] * 4);
+        unsigned char *pt = reinterpret_cast<unsigned char *>(ctx->pinned + off);
+        off += arena_sz((size_t)n[s] * n[s]);
         MODEST_REQUIRE(n[s] == 0 || (boxes_host[s] && out_host[s]), "NULL buffer");
         for (int i = 0; i < n[s]; ++i) {   // the host's libm evaluates the trig (modest_boxes_iou_bev_host)
             float *d = pb + (size_t)i * 11;
@@ -405,6 +494,7 @@ int modest_boxes_self_iou_bev_host_batch(modest_ctx *ctx, const float *const *bo
         }
         sets[s].boxes = pb;
         sets[s].out = po;
+        sets[s].ties = pt;
         sets[s].n = n[s];
         sets[s].pad = 0;
         outs[(size_t)s] = po;
@@ -413,7 +503,10 @@ int modest_boxes_self_iou_bev_host_batch(modest_ctx *ctx, const float *const *bo
     MODEST_HIP_CHECK(hipGetLastError());
     MODEST_HIP_CHECK(hipStreamSynchronize(as_stream(stream_)));
     for (int s = 0; s < B; ++s)
-        if (n[s] > 0) memcpy(out_host[s], outs[(size_t)s], (size_t)n[s] * n[s] * 4);
+        if (n[s] > 0) {
+            host_resolve_ties(sets[s].boxes, n[s], sets[s].boxes, n[s], outs[(size_t)s], sets[s].ties);
+            memcpy(out_host[s], outs[(size_t)s], (size_t)n[s] * n[s] * 4);
+        }
     return MODEST_OK;
 }
 
@@ -430,12 +523,13 @@ extern "C" int modest_boxes_iou_bev_host(modest_ctx *ctx, const float *a_host, i
     // path (iou3d_cpu.cpp:128-133) calls, not the device's -- and the kernel reads them and writes the
     // matrix there directly (a few hundred bytes each way): one launch, one stream sync, no copies.
     const size_t ba = arena_sz((size_t)na * 44), bb = arena_sz((size_t)nb * 44);
-    const size_t bo = arena_sz((size_t)na * nb * 4);
-    int rc = modest_ctx_reserve_pinned(ctx, ba + bb + bo);
+    const size_t bo = arena_sz((size_t)na * nb * 4), bt = arena_sz((size_t)na * nb);
+    int rc = modest_ctx_reserve_pinned(ctx, ba + bb + bo + bt);
     if (rc) return rc;
     float *pa = reinterpret_cast<float *>(ctx->pinned);
     float *pb = reinterpret_cast<float *>(ctx->pinned + ba);
     float *pout = reinterpret_cast<float *>(ctx->pinned + ba + bb);
+    unsigned char *pties = reinterpret_cast<unsigned char *>(ctx->pinned + ba + bb + bo);
     auto stage = [](float *dst, const float *src, int n) {
         for (int i = 0; i < n; ++i) {
             float *d = dst + (size_t)i * 11;
@@ -451,10 +545,11 @@ extern "C" int modest_boxes_iou_bev_host(modest_ctx *ctx, const float *a_host, i
     stage(pb, b_host, nb);
     {
         const long long total = (long long)na * nb;
-        pair_kernel<true, true><<<(int)((total + NMS_TPB - 1) / NMS_TPB), NMS_TPB, 0, as_stream(stream_)>>>(pa, na, pb, nb, pout);
+        pair_kernel<true, true><<<(int)((total + NMS_TPB - 1) / NMS_TPB), NMS_TPB, 0, as_stream(stream_)>>>(pa, na, pb, nb, pout, pties);
         MODEST_HIP_CHECK(hipGetLastError());
     }
     MODEST_HIP_CHECK(hipStreamSynchronize(as_stream(stream_)));
+    host_resolve_ties(pa, na, pb, nb, pout, pties);
     memcpy(out_host, pout, (size_t)na * nb * 4);
     return MODEST_OK;
 }

@@ -7,11 +7,35 @@
  * (oracle/Makefile).  Validated against the reference's own iou3d_cpu.cpp
  * compiled where it lies (oracle/build_ref.py -> oracle/_ref/iou3d_ref.so) and
  * against tests/golden/boxes_iou.npz in tests/test_oracle_mask.py (test_iou_oracle_*).
+ *
+ * -DMODEST_ORACLE_TRIG_F64 builds the "f64 twin" (libiou3d_oracle_f64.so): the
+ * three libm calls become the double function rounded once to float, which is
+ * what modest_amd/csrc/trig_f32.h evaluates on the device.  Nothing else changes,
+ * so the twin is the device-trig kernels' arithmetic on the host
+ * (tests/test_iou3d_oracle_cpu.py ties it to this build and to exact geometry).
+ * -DMODEST_ORACLE_ATAN2_F64 replaces atan2f alone (libiou3d_oracle_atan2_f64.so):
+ * what the host-trig kernels (host cosf / sinf, the device's atan2) compute BEFORE
+ * the host resolves their near-tied vertex angles with atan2f.  Tests use it only
+ * to show that an input holds pairs on which that resolution decides the value.
  */
 #include <math.h>
 #include <stdint.h>
 
 #define EPSF 1e-8f
+
+#ifdef MODEST_ORACLE_TRIG_F64
+static float trig_cos(float x) { return (float)cos((double)x); }
+static float trig_sin(float x) { return (float)sin((double)x); }
+static float trig_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
+#else
+static float trig_cos(float x) { return cosf(x); }
+static float trig_sin(float x) { return sinf(x); }
+#ifdef MODEST_ORACLE_ATAN2_F64
+static float trig_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
+#else
+static float trig_atan2(float y, float x) { return atan2f(y, x); }
+#endif
+#endif
 
 typedef struct { float x, y; } P2;
 
@@ -30,7 +54,7 @@ static int rect_cross(P2 p1, P2 p2, P2 q1, P2 q2) {                             
 static int in_box2d(const float *box, P2 p) {                                     /* cpp:74-84 */
     const float MARGIN = 1e-2f;
     float cx = box[0], cy = box[1];
-    float c = cosf(-box[6]), s = sinf(-box[6]);
+    float c = trig_cos(-box[6]), s = trig_sin(-box[6]);
     float rx = (p.x - cx) * c + (p.y - cy) * (-s);
     float ry = (p.x - cx) * s + (p.y - cy) * c;
     return fabsf(rx) < box[3] / 2 + MARGIN && fabsf(ry) < box[4] / 2 + MARGIN;
@@ -67,7 +91,7 @@ float modest_oracle_box_overlap(const float *a, const float *b) {               
     P2 ca = {a[0], a[1]}, cb = {b[0], b[1]};
     P2 A[5] = {{a[0] - adx, a[1] - ady}, {a[0] + adx, a[1] - ady}, {a[0] + adx, a[1] + ady}, {a[0] - adx, a[1] + ady}};
     P2 B[5] = {{b[0] - bdx, b[1] - bdy}, {b[0] + bdx, b[1] - bdy}, {b[0] + bdx, b[1] + bdy}, {b[0] - bdx, b[1] + bdy}};
-    float ac = cosf(aa), as = sinf(aa), bc = cosf(ba), bs = sinf(ba);
+    float ac = trig_cos(aa), as = trig_sin(aa), bc = trig_cos(ba), bs = trig_sin(ba);
     for (int k = 0; k < 4; k++) { rot(ca, ac, as, &A[k]); rot(cb, bc, bs, &B[k]); }
     A[4] = A[0]; B[4] = B[0];
     P2 poly[24], ctr = {0.f, 0.f};
@@ -84,7 +108,7 @@ float modest_oracle_box_overlap(const float *a, const float *b) {               
     ctr.x /= cnt; ctr.y /= cnt;
     for (int j = 0; j < cnt - 1; j++)
         for (int i = 0; i < cnt - j - 1; i++)
-            if (atan2f(poly[i].y - ctr.y, poly[i].x - ctr.x) > atan2f(poly[i + 1].y - ctr.y, poly[i + 1].x - ctr.x)) {
+            if (trig_atan2(poly[i].y - ctr.y, poly[i].x - ctr.x) > trig_atan2(poly[i + 1].y - ctr.y, poly[i + 1].x - ctr.x)) {
                 P2 t = poly[i]; poly[i] = poly[i + 1]; poly[i + 1] = t;
             }
     float area = 0;

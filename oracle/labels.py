@@ -5,6 +5,11 @@ gen_label_files.py`` with ``utils/pointcloud_utils.py:320-379`` and the
 calibration/box helpers of ``utils/kitti_util.py`` (reference checkout).
 BEV IoU comes from oracle/iou3d_oracle.c (plain-C restatement) or, where
 present, from the reference's own iou3d_cpu.cpp build (oracle/_ref).
+``arith="f64"`` selects the f64 twin of the C restatement (the same file built
+with -DMODEST_ORACLE_TRIG_F64: cos / sin / atan2 in double, rounded once), which
+is the arithmetic of the kernels that evaluate their trig on the device.
+``arith="atan2_f64"`` replaces atan2f alone: the host-trig kernels before the
+host resolves their near-tied vertex angles (a probe for test inputs, no yardstick).
 """
 from __future__ import annotations
 
@@ -16,13 +21,15 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
+_LIBS = {}
+_SO = {"glibc": "libiou3d_oracle.so", "f64": "libiou3d_oracle_f64.so", "atan2_f64": "libiou3d_oracle_atan2_f64.so"}
 
 
-def _lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(HERE, "_build", "libiou3d_oracle.so")
+def _lib(arith="glibc"):
+    if arith not in _SO:
+        raise ValueError(f"arith must be one of {sorted(_SO)}, got {arith!r}")
+    if arith not in _LIBS:
+        so = os.path.join(HERE, "_build", _SO[arith])
         if not os.path.exists(so):
             subprocess.run(["make", "-C", HERE], check=True, capture_output=True)
         lib = ctypes.CDLL(so)
@@ -31,16 +38,17 @@ def _lib():
         lib.modest_oracle_boxes_bev.restype = None
         lib.modest_oracle_nms.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
         lib.modest_oracle_nms.restype = ctypes.c_int
-        _LIB = lib
-    return _LIB
+        _LIBS[arith] = lib
+    return _LIBS[arith]
 
 
-def boxes_iou_bev(boxes_a, boxes_b, overlap_only=False):
-    """iou3d_nms_utils.boxes_iou_bev (utils/iou3d_nms/iou3d_nms_utils.py:37-51)."""
+def boxes_iou_bev(boxes_a, boxes_b, overlap_only=False, arith="glibc"):
+    """iou3d_nms_utils.boxes_iou_bev (utils/iou3d_nms/iou3d_nms_utils.py:37-51); arith: "glibc" (cosf / sinf / atan2f)
+    or "f64" (the twin: double trig rounded once, as the device-trig kernels evaluate it)."""
     a = np.ascontiguousarray(boxes_a, dtype=np.float32)
     b = np.ascontiguousarray(boxes_b, dtype=np.float32)
     out = np.zeros((a.shape[0], b.shape[0]), dtype=np.float32)
-    _lib().modest_oracle_boxes_bev(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], out.ctypes.data,
+    _lib(arith).modest_oracle_boxes_bev(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], out.ctypes.data,
                                    1 if overlap_only else 0)
     return out
 
@@ -61,11 +69,11 @@ def boxes_iou_bev_reference(boxes_a, boxes_b):
     return out.numpy()
 
 
-def nms(boxes_sorted, thresh, rotated=True):
-    """nms_gpu / nms_normal_gpu (src/iou3d_nms.cpp:90-186) on score-sorted boxes."""
+def nms(boxes_sorted, thresh, rotated=True, arith="glibc"):
+    """nms_gpu / nms_normal_gpu (src/iou3d_nms.cpp:90-186) on score-sorted boxes; arith as in boxes_iou_bev."""
     b = np.ascontiguousarray(boxes_sorted, dtype=np.float32)
     keep = np.zeros(b.shape[0], dtype=np.int64)
-    k = _lib().modest_oracle_nms(b.ctypes.data, b.shape[0], ctypes.c_float(thresh), 1 if rotated else 0,
+    k = _lib(arith).modest_oracle_nms(b.ctypes.data, b.shape[0], ctypes.c_float(thresh), 1 if rotated else 0,
                                  keep.ctypes.data)
     return keep[:k]
 
