@@ -226,6 +226,20 @@ __device__ __forceinline__ void block_sums(double (&v)[NV], TrialShared &T) {
     __syncthreads();
 }
 
+// block-wide minimum and maximum (lo, hi: this thread's; on return the block's, in every thread)
+__device__ __forceinline__ void block_minmax(double &lo, double &hi, TrialShared &T) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, off));
+        hi = fmax(hi, __shfl_down(hi, off));
+    }
+    if (lane == 0) T.part[w][0] = lo, T.part[w][1] = hi;
+    __syncthreads();
+    lo = T.part[0][0], hi = T.part[0][1];
+    for (int u = 1; u < GP_WAVES; ++u) lo = fmin(lo, T.part[u][0]), hi = fmax(hi, T.part[u][1]);
+    __syncthreads();   // T.part is the next block_sums' to write
+}
+
 // exact plane y = c0 x + c1 z + b through three candidates: centred 2x2 normal equations (the host mirror states the same
 // operations in the same order); false when the triplet is collinear in (x, z) (sklearn's lstsq takes the minimum norm)
 __device__ bool triplet_plane(const double *cx, const double *cz, const double *cy, const int *t, double *m) {
@@ -333,7 +347,7 @@ __device__ int fit_frame(const double *cx, const double *cz, const double *cy, i
     if (s_flag) return s_flag;
     // refit over the consensus set of the winner: means, then centred moments
     const double m[3] = {s_best[0], s_best[1], s_best[2]};
-    double s1[4] = {0.0, 0.0, 0.0, 0.0};
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, ylo = INFINITY, yhi = -INFINITY;
     for (int i = tid; i < n; i += GP_THREADS) {
         const double x = cx[i], z = cz[i], y = cy[i];
         if (fabs(y - gp_pred(x, z, m)) <= thr) {
@@ -341,11 +355,13 @@ __device__ int fit_frame(const double *cx, const double *cz, const double *cy, i
             s1[1] += x;
             s1[2] += z;
             s1[3] += y;
+            ylo = fmin(ylo, y), yhi = fmax(yhi, y);
         }
     }
     block_sums<4>(s1, T);
     const double cnt = T.tot[0], mx = T.tot[1] / cnt, mz = T.tot[2] / cnt, my = T.tot[3] / cnt;
     __syncthreads();   // T.tot is rewritten below
+    block_minmax(ylo, yhi, T);
     double s2[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = tid; i < n; i += GP_THREADS) {
         const double x = cx[i], z = cz[i], y = cy[i];
@@ -363,7 +379,9 @@ __device__ int fit_frame(const double *cx, const double *cz, const double *cy, i
         const double sxx = T.tot[0], sxz = T.tot[1], szz = T.tot[2], sxy = T.tot[3], szy = T.tot[4];
         const double det = sxx * szz - sxz * sxz;
         R.n_inliers = (int)cnt;
-        if (!(cnt >= 3.0) || !(fabs(det) > 1e-12 * fmax(sxx * szz, 1e-300))) {
+        // a consensus set of ONE height has sxy = szy = 0 in exact arithmetic: its slopes are the rounding of the sums, in
+        // the order they are added, and {:e} prints them, so the frame is the host's to fit and to print
+        if (!(cnt >= 3.0) || !(fabs(det) > 1e-12 * fmax(sxx * szz, 1e-300)) || !(ylo < yhi)) {
             s_flag = MODEST_GP_HOST;
         } else {
             const double c0 = (sxy * szz - szy * sxz) / det;

@@ -899,7 +899,12 @@ def ground_planes(rows: torch.Tensor, frames: np.ndarray, min_h: float, max_h: f
                   ctx: Optional[Context] = None):
     """RANSAC.py's fit of a batch of frames (modest_ground_planes).  rows: packed (R,4) float32 device rows;
     frames: GP_FRAME array (row offset, n, calibration, generator), updated in place with the advanced generators.
-    Returns (GP_RESULT array, GPU milliseconds of the batch, triplets (F, max_trials, 3) int32 or None)."""
+    Returns (GP_RESULT array, GPU milliseconds of the batch, triplets (F, max_trials, 3) int32 or None).
+    A GP_HOST row always holds n_cand, and median / mad above 300 candidates.  One handed back during its trials (a
+    collinear triplet, a trial bound next to an integer) also holds n_trials and the triplet rows drawn so far; one
+    handed back at the refit (a consensus set of fewer than three points, a collinear one, or one of one height) holds
+    the n_trials, n_inliers and triplet rows of the finished trial loop.  Rows handed back by the candidate count, and
+    the chained rows after a hand-back, hold n_trials = 0 and no triplets.  The plane of a GP_HOST row is not a fit."""
     lib = load()
     _dev(rows, torch.float32, "rows")
     assert rows.ndim == 2 and rows.shape[1] == 4
