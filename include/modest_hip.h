@@ -914,6 +914,27 @@ int modest_pn2_three_interpolate(int b, int c, int m, int n, const float *points
 int modest_pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out_dev, const int32_t *idx_dev,
                                       const float *weight_dev, float *grad_points_dev, void *stream);
 
+/* ---- a23 roipoint_pool3d_cuda.forward and roiaware_pool3d_cuda.points_in_boxes_gpu -------------------------------
+ * The two box-membership ops of PointRCNN.  Every buffer [dev], float32 / int32, contiguous; enqueue only, no context,
+ * no device allocation, no synchronise.  Element offsets are 64-bit.  Both use one predicate (check_pt_in_box3d,
+ * roipoint_pool3d_kernel.cu:22-35 = roiaware_pool3d_kernel.cu:23-36); its arithmetic is the contract of DESIGN.md
+ * section 7e: float32 differences, products and sums without contraction, cos / sin of -rz as the rounded double
+ * functions, the three comparisons decided exactly as the reference's double expressions.
+ *
+ * roipoint_pool3d_kernel.cu:38-165 roipool3dLauncher.  xyz (b,n,3), boxes (b,m,7) [cx,cy,cz,dx,dy,dz,rz],
+ * feat (b,n,c), pooled (b,m,s,3+c), empty_flag (b,m).  Per box the first s inside points in index order; with
+ * 0 < cnt < s slot k >= cnt repeats slot k % cnt; a row is xyz[idx] followed by feat[idx], bit for bit.  cnt == 0 sets
+ * the box's flag to 1 and leaves its rows as given; a box with an inside point keeps its flag, and its rows are written
+ * only if that flag is 0 (the caller zero-fills both, as the reference's Python side does).  No (n, m) intermediate.
+ * c == 0 is legal; b == 0 or m == 0 writes nothing; n == 0 or s == 0 sets every flag to 1.  s <= 15360.            */
+int modest_roipoint_pool3d(int b, int n, int m, int c, int s, const float *xyz_dev, const float *boxes_dev,
+                           const float *feat_dev, float *pooled_dev, int32_t *empty_flag_dev, void *stream);
+/* roiaware_pool3d_kernel.cu:313-355 points_in_boxes_launcher.  boxes (b,m,7), pts (b,n,3) -> box_idx (b,n): the lowest
+ * index of a box that contains the point; a point in no box is left as given (the caller fills -1).  An all-zero
+ * (padding) box contains a point with z == 0 within 1e-5 of the origin in x and y.  Any size 0 writes nothing.      */
+int modest_points_in_boxes(int b, int m, int n, const float *boxes_dev, const float *pts_dev, int32_t *box_idx_dev,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

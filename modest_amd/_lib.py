@@ -105,6 +105,8 @@ SIGNATURES = {
     "modest_pn2_three_nn": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_pn2_three_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_pn2_three_interpolate_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_roipoint_pool3d": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "modest_points_in_boxes": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
 }
 
 _lib = None

@@ -1,0 +1,58 @@
+"""Bind this library's drop-in modules under the names the MODEST and OpenPCDet sources import.
+
+    from modest_amd.utils import pcdet_bind
+    pcdet_bind.install()          # before `import pcdet.models` / `import pcdet.datasets`
+
+registers, in ``sys.modules``, the four extension shims PointRCNN is built from and the evaluation module, and -- with
+``stand_ins=True`` -- stand-in modules for what ``import pcdet.models`` loads but no model of the reference's scripts
+calls.  Any attribute of a stand-in is a class that can be named and subclassed at import time and raises
+``NotImplementedError`` when it is called.  Calling ``install`` again changes nothing.  Nothing here touches the GPU:
+the shims open the library at their first call.
+"""
+import importlib
+import importlib.util
+import sys
+import types
+
+SHIMS = {
+    "iou3d_nms_cuda": "modest_amd.utils.iou3d_nms.iou3d_nms_cuda",
+    "pcdet.ops.iou3d_nms.iou3d_nms_cuda": "modest_amd.utils.iou3d_nms.iou3d_nms_cuda",
+    "pcdet.ops.pointnet2.pointnet2_batch.pointnet2_batch_cuda":
+        "modest_amd.utils.pointnet2.pointnet2_batch.pointnet2_batch_cuda",
+    "pcdet.ops.roipoint_pool3d.roipoint_pool3d_cuda": "modest_amd.utils.roipoint_pool3d.roipoint_pool3d_cuda",
+    "pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda": "modest_amd.utils.roiaware_pool3d_cuda",
+    "pcdet.datasets.kitti.kitti_object_eval_python.eval": "modest_amd.kitti_eval",
+}
+STAND_INS = ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda", "spconv")
+
+
+class StandIn(types.ModuleType):
+    """a module that is not provided: it imports, and whatever is taken from it fails when called"""
+
+    def __getattr__(self, name):
+        if name.startswith("__") and name.endswith("__"):
+            raise AttributeError(name)
+        module = self.__name__
+
+        def __init__(self, *args, **kwargs):
+            raise NotImplementedError(f"{module}.{name} is not provided by modest_amd (PV-RCNN / PartA2 only)")
+
+        missing = type(name, (), {"__init__": __init__, "__module__": module})
+        setattr(self, name, missing)
+        return missing
+
+
+def install(stand_ins=True):
+    """-> {name: module} of everything bound (also what an earlier call bound)"""
+    bound = {}
+    for name, target in SHIMS.items():
+        bound[name] = sys.modules[name] = importlib.import_module(target)
+    if stand_ins:
+        for name in STAND_INS:
+            mod = sys.modules.get(name)
+            if mod is None and "." not in name and importlib.util.find_spec(name) is not None:
+                continue   # the real package is installed: leave it alone
+            if mod is None:
+                mod = sys.modules[name] = StandIn(name)
+            bound[name] = mod
+    return bound

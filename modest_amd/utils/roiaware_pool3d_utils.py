@@ -1,8 +1,13 @@
-"""``points_in_boxes_cpu`` of OpenPCDet's ops/roiaware_pool3d/roiaware_pool3d_utils.py:9-27 (whose compiled half is a CUDA
-extension) on the GPU: the dense (num_boxes, num_points) int32 membership mask that ``create_groundtruth_database``, the
-``gt_sampling`` augmentor and users' scripts ask for.  Same predicate, bit for bit, as
+"""``points_in_boxes_cpu`` and ``points_in_boxes_gpu`` of OpenPCDet's ops/roiaware_pool3d/roiaware_pool3d_utils.py:9-41
+(whose compiled half is a CUDA extension), both on the GPU.
+
+``points_in_boxes_cpu`` is the dense (num_boxes, num_points) int32 membership mask that ``create_groundtruth_database``,
+the ``gt_sampling`` augmentor and users' scripts ask for.  Same predicate, bit for bit, as
 ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-168; computed by csrc/kitti_infos.hip (``ops.infos_count``).
-``points_in_boxes_gpu`` and the RoI pooling are not provided (the PointNet++ ops are in ``utils/pointnet2``)."""
+
+``points_in_boxes_gpu`` is the batched (B, num_points) index of the first box that holds each point, the point head's
+target assignment (csrc/roipool.hip).  The RoI point pooling is ``utils/roipoint_pool3d``, the
+PointNet++ ops are ``utils/pointnet2``; the RoI-aware voxel pooling of PartA2 (``RoIAwarePool3d``) is not provided."""
 import numpy as np
 import torch
 
@@ -41,3 +46,19 @@ def points_in_boxes_cpu(points, boxes):
     st = ops.infos_count(rows, n, fr, tab, und_cap=0, dense_stride=n)
     out = st.dense[:nb].to(out_dev)
     return out.numpy() if is_numpy else out
+
+
+def points_in_boxes_gpu(points, boxes):
+    """
+    :param points: (B, M, 3)
+    :param boxes: (B, T, 7), num_valid_boxes <= T
+    :return box_idxs_of_pts: (B, M) int32, the lowest index of a box that holds the point, background = -1
+    """
+    from . import roiaware_pool3d_cuda
+    assert boxes.shape[0] == points.shape[0]
+    assert boxes.shape[2] == 7 and points.shape[2] == 3
+    batch_size, num_points, _ = points.shape
+
+    box_idxs_of_pts = points.new_zeros((batch_size, num_points), dtype=torch.int).fill_(-1)
+    roiaware_pool3d_cuda.points_in_boxes_gpu(boxes.contiguous(), points.contiguous(), box_idxs_of_pts)
+    return box_idxs_of_pts
