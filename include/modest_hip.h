@@ -935,6 +935,41 @@ int modest_roipoint_pool3d(int b, int n, int m, int c, int s, const float *xyz_d
 int modest_points_in_boxes(int b, int m, int n, const float *boxes_dev, const float *pts_dev, int32_t *box_idx_dev,
                            void *stream);
 
+/* ---- a24 point-to-voxel grouping for PointPillars (spconv.utils.VoxelGenerator) ---------------
+ * spconv 1.2's hard voxelisation, first come first served.  lo3 / vs3: the lower corner of the point cloud range and the
+ * voxel size as float32, grid3 = [nx, ny, nz] (round((hi - lo) / vs) in float32, the caller's), at most 2^31 - 1 cells.
+ * Point i lies in cell c_j = floorf((p_j - lo_j) / vs_j) (float32, a correctly rounded division) and is dropped unless
+ * 0 <= c_j < (float)grid_j on all three axes (tested on the float: NaN and +-inf are dropped, -0.0 is cell 0).  Points
+ * are walked in order; a cell that no earlier point opened becomes the next voxel unless max_voxels are open (the point
+ * is dropped, the walk goes on); a point takes its voxel's next slot unless max_num_points are taken.
+ *
+ * Host path, one cloud: points [host] (n, c) float32, c >= 3, xyz first.  table [host] (cells) int32, all -1 on entry
+ * and again on return (the caller allocates it once per generator).  Outputs [host], capacity max_voxels rows, may be
+ * uninitialised: voxels (V, P, c) rows as raw words and +0.0 in unused slots, coords (V, 3) [z, y, x], num_points (V),
+ * point_mask (V, P) the index of the point in each slot or -1.  Returns V, or a negative error.  No HIP call.         */
+int64_t modest_voxelize_host(const float *points_host, int64_t n, int c, const float *lo3, const float *vs3,
+                             const int32_t *grid3, int max_num_points, int max_voxels, int32_t *table_host,
+                             float *voxels_host, int32_t *coords_host, int32_t *num_points_host, int32_t *point_mask_host);
+/* Device path, a collated batch: points [dev] (n_rows, 1 + c) float32 with the batch index in column 0, integers in
+ * [0, batch_cap) in non-decreasing order (anything else is found on the device and fails the plan call); max_voxels
+ * applies per cloud.  Scratch is the caller's: workspace [dev], 256-byte aligned, modest_voxelize_workspace_bytes bytes
+ * -- a function of n_rows and batch_cap only (grid3 is checked, a grid of more than 2^31 - 1 cells returns -1).  No
+ * device allocation, no context; nothing depends on the order in which atomics land.
+ * plan: enqueues everything up to the voxel counts and synchronises the stream ONCE.  counts [PINNED host]
+ * (4 + batch_cap) int32, written by the last kernel itself: [0] error bits, [1] clouds seen (last batch index + 1),
+ * [2] cells opened in the batch, [3] sum of V_b, [4 + b] V_b = min(cells of cloud b, max_voxels).
+ * fill: enqueue only, on the same stream and workspace, same arguments, cells_opened = counts[2] and total_voxels =
+ * counts[3].  Writes EVERY element of voxels (total, P, c), coords (total, 4) [b, z, y, x], num_points (total) and
+ * point_mask (total, P) (row indices into points); clouds in batch order, voxels in the order they were opened.     */
+int64_t modest_voxelize_workspace_bytes(int64_t n_rows, int batch_cap, const int32_t *grid3_host);
+int modest_voxelize_plan(const float *points_dev, int64_t n_rows, int c, int batch_cap, const float *lo3_host,
+                         const float *vs3_host, const int32_t *grid3_host, int max_num_points, int max_voxels,
+                         void *workspace_dev, int64_t workspace_bytes, int32_t *counts_pinned_host, void *stream);
+int modest_voxelize_fill(const float *points_dev, int64_t n_rows, int c, int batch_cap, const int32_t *grid3_host,
+                         int max_num_points, int max_voxels, const void *workspace_dev, int64_t workspace_bytes,
+                         int32_t cells_opened, int64_t total_voxels, float *voxels_dev, int32_t *coords_dev,
+                         int32_t *num_points_dev, int32_t *point_mask_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

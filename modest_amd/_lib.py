@@ -107,6 +107,12 @@ SIGNATURES = {
     "modest_pn2_three_interpolate_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_roipoint_pool3d": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP]),
     "modest_points_in_boxes": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_voxelize_host": (C.c_int64, [VP, C.c_int64, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_voxelize_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, VP]),
+    "modest_voxelize_plan": (C.c_int, [VP, C.c_int64, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, C.c_int64, VP,
+                                       VP]),
+    "modest_voxelize_fill": (C.c_int, [VP, C.c_int64, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP, C.c_int64, C.c_int32,
+                                       C.c_int64, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

@@ -1040,3 +1040,105 @@ def infos_gather(st: InfosBatch) -> np.ndarray:
                                   _np_ptr(db_count) if st.n_boxes else _np_ptr(np.zeros(1, dtype=np.int32)),
                                   _np_ptr(base), out.data_ptr(), total, _stream()), "modest_infos_gather")
     return out[:total].cpu().numpy()
+
+
+# --------------------------------------------------------------------------- point-to-voxel grouping
+VOXELIZE_DEFAULT_BATCH_CAP = 256   # clouds a batch may hold when the caller does not say how many it has
+
+
+def voxelize_workspace_bytes(n_rows: int, batch_size: int, grid_size) -> int:
+    """scratch bytes of `voxelize` for n_rows stacked rows: does not depend on the grid (which is only checked)"""
+    g = np.ascontiguousarray(grid_size, dtype=np.int32)
+    assert g.shape == (3,)
+    nb = int(load().modest_voxelize_workspace_bytes(int(n_rows), int(batch_size), _np_ptr(g)))
+    if nb < 0:
+        check(nb, "modest_voxelize_workspace_bytes")
+    return nb
+
+
+class VoxelizeGeometry:
+    """float32 lower corner and voxel size, the int32 grid [nx, ny, nz], as the C ABI takes them"""
+
+    def __init__(self, voxel_size, point_cloud_range):
+        from .utils.spconv_utils import grid_size_f32
+        self.lo, self.vs, self.grid_size = grid_size_f32(voxel_size, point_cloud_range)
+        self.grid32 = np.ascontiguousarray(self.grid_size, dtype=np.int32)
+
+
+class VoxelizePlan:
+    """what `voxelize_plan` leaves for `voxelize_fill`: the arguments, the workspace and the counts read back"""
+
+
+def voxelize_plan(points: torch.Tensor, voxel_size, point_cloud_range, max_num_points: int, max_voxels: int,
+                  batch_size: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+                  counts_pinned: Optional[torch.Tensor] = None, geometry: Optional[VoxelizeGeometry] = None) -> VoxelizePlan:
+    """modest_voxelize_plan on PyTorch's current stream: everything up to the per-cloud voxel counts, ONE stream
+    synchronise.  Arguments as `voxelize`.  -> plan with .counts (B,) int32 numpy = V_b and .total = their sum."""
+    lib = load()
+    _dev(points, torch.float32, "points")
+    if points.ndim != 2 or points.shape[1] < 4:
+        raise ValueError(f"points has shape {tuple(points.shape)}, expected (N, 1 + C) with C >= 3")
+    pl = VoxelizePlan()
+    pl.geo = geo = geometry if geometry is not None else VoxelizeGeometry(voxel_size, point_cloud_range)
+    pl.points, pl.n, pl.c = points, int(points.shape[0]), int(points.shape[1]) - 1
+    pl.p, pl.m = int(max_num_points), int(max_voxels)
+    pl.cap = cap = VOXELIZE_DEFAULT_BATCH_CAP if batch_size is None else int(batch_size)
+    if cap < 1:
+        raise ValueError("batch_size must be positive")
+    dev = points.device
+    nbytes = voxelize_workspace_bytes(pl.n, cap, geo.grid32)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    pl.workspace = _dev(workspace, torch.uint8, "workspace")
+    if counts_pinned is None or counts_pinned.numel() < 4 + cap:
+        counts_pinned = torch.empty((4 + cap,), dtype=torch.int32).pin_memory()
+    if counts_pinned.dtype != torch.int32 or not counts_pinned.is_pinned():
+        raise ValueError("counts_pinned must be a pinned int32 host tensor")
+    pl.counts_pinned = counts_pinned
+    with torch.cuda.device(dev):
+        check(lib.modest_voxelize_plan(points.data_ptr(), pl.n, pl.c, cap, _np_ptr(geo.lo), _np_ptr(geo.vs), _np_ptr(geo.grid32),
+                                       pl.p, pl.m, workspace.data_ptr(), workspace.numel(), counts_pinned.data_ptr(), _stream()),
+              "modest_voxelize_plan")
+    head = counts_pinned[:4].tolist()
+    nb = head[1] if batch_size is None else cap
+    pl.counts = counts_pinned[4:4 + nb].numpy().copy()
+    pl.opened, pl.total = head[2], head[3]
+    return pl
+
+
+def voxelize_fill(pl: VoxelizePlan, voxels: Optional[torch.Tensor] = None, coords: Optional[torch.Tensor] = None,
+                  num_points: Optional[torch.Tensor] = None, point_mask: Optional[torch.Tensor] = None):
+    """modest_voxelize_fill (enqueue only, the stream of the plan call): writes every element of the four outputs,
+    (total, P, C) float32, (total, 4) int32, (total,) int32, (total, P) int32 -- allocated here unless given."""
+    dev = pl.points.device
+    shapes = ((pl.total, pl.p, pl.c), (pl.total, 4), (pl.total,), (pl.total, pl.p))
+    dtypes = (torch.float32, torch.int32, torch.int32, torch.int32)
+    outs = []
+    for t, shape, dtype, name in zip((voxels, coords, num_points, point_mask), shapes, dtypes,
+                                     ("voxels", "coords", "num_points", "point_mask")):
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        _dev(t, dtype, name)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, the plan says {shape}")
+        outs.append(t)
+    with torch.cuda.device(dev):
+        check(load().modest_voxelize_fill(pl.points.data_ptr(), pl.n, pl.c, pl.cap, _np_ptr(pl.geo.grid32), pl.p, pl.m,
+                                          pl.workspace.data_ptr(), pl.workspace.numel(), pl.opened, pl.total,
+                                          *(t.data_ptr() for t in outs), _stream()), "modest_voxelize_fill")
+    return tuple(outs)
+
+
+def voxelize(points: torch.Tensor, voxel_size, point_cloud_range, max_num_points: int, max_voxels: int,
+             batch_size: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+             counts_pinned: Optional[torch.Tensor] = None, geometry: Optional[VoxelizeGeometry] = None):
+    """spconv's hard voxelisation of a collated batch on the device, as `collate_batch` would have stacked the per-cloud
+    host results.  points (sum N, 1 + C) float32, batch index in column 0, non-decreasing; max_voxels per cloud.
+    -> voxels (sum V, P, C) float32, voxel_coords (sum V, 4) int32 [b, z, y, x], voxel_num_points (sum V,) int32,
+    voxel_point_mask (sum V, P) int32 (row indices into points, -1 in unused slots), counts (B,) int32 numpy = V_b.
+    batch_size None: the clouds seen (last batch index + 1, at most 256).  One stream synchronise (the counts size the
+    outputs); workspace (uint8, device) and counts_pinned (int32, pinned) are reused when given and large enough.
+    A batch column that is out of order or not integral raises and produces nothing."""
+    pl = voxelize_plan(points, voxel_size, point_cloud_range, max_num_points, max_voxels, batch_size, workspace,
+                       counts_pinned, geometry)
+    return (*voxelize_fill(pl), pl.counts)

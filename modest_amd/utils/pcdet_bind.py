@@ -5,8 +5,9 @@
 
 registers, in ``sys.modules``, the four extension shims PointRCNN is built from and the evaluation module, and -- with
 ``stand_ins=True`` -- stand-in modules for what ``import pcdet.models`` loads but no model of the reference's scripts
-calls.  Any attribute of a stand-in is a class that can be named and subclassed at import time and raises
-``NotImplementedError`` when it is called.  Calling ``install`` again changes nothing.  Nothing here touches the GPU:
+calls.  The ``spconv`` stand-in carries one real part, ``spconv.utils`` with the host voxel generators PointPillars'
+data pipeline constructs (``modest_amd.utils.spconv_utils``); an installed spconv is left alone.  Any other attribute of
+a stand-in is a class that can be named and subclassed at import time and raises ``NotImplementedError`` when it is called.  Calling ``install`` again changes nothing.  Nothing here touches the GPU:
 the shims open the library at their first call.
 """
 import importlib
@@ -24,6 +25,7 @@ SHIMS = {
     "pcdet.datasets.kitti.kitti_object_eval_python.eval": "modest_amd.kitti_eval",
 }
 STAND_INS = ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda", "spconv")
+SPCONV_UTILS = "modest_amd.utils.spconv_utils"   # bound as spconv.utils while spconv itself is a stand-in
 
 
 class StandIn(types.ModuleType):
@@ -55,4 +57,9 @@ def install(stand_ins=True):
             if mod is None:
                 mod = sys.modules[name] = StandIn(name)
             bound[name] = mod
+        spconv = sys.modules.get("spconv")
+        if isinstance(spconv, StandIn):   # the one part of spconv that is provided: the voxel generators (PointPillars)
+            utils = importlib.import_module(SPCONV_UTILS)
+            spconv.utils = utils
+            sys.modules["spconv.utils"] = utils   # `from spconv.utils import ...`: a stand-in has no __path__ to search
     return bound
