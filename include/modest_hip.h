@@ -970,6 +970,44 @@ int modest_voxelize_fill(const float *points_dev, int64_t n_rows, int c, int bat
                          int32_t cells_opened, int64_t total_voxels, float *voxels_dev, int32_t *coords_dev,
                          int32_t *num_points_dev, int32_t *point_mask_dev, void *stream);
 
+/* ---- a25 sparse 3-D convolutions for SECOND (spconv 1.2's SubMConv3d / SparseConv3d) -----------
+ * indices [dev] (n_in, 4) int32 [b, z, y, x], unique rows inside batch_size x shape3 = [D, H, W]; kernel3 / stride3 / pad3
+ * in the same axis order, kernel sizes 1 .. 7.  subm != 0: odd kernels, stride and padding ignored, the output sites are
+ * the input sites in input order.  Otherwise out_j = (in_j + 2 p_j - k_j) / s_j + 1 and output site o exists iff some
+ * input i and offset k satisfy i = o * s - p + k; output rows ascend in (b, z, y, x).  Offset k = (kz * ky + ky_i) * kx + kx_i.
+ * Sites are 64-bit keys: batch_size * D * H * W may exceed 2^32 (at most 2^56), no table over the grid is allocated.
+ * Scratch is the caller's: workspace [dev], 256-byte aligned, modest_spconv_rulebook_workspace_bytes(n_in, kernel volume,
+ * subm) bytes.  No device allocation, no context, nothing depends on the order in which atomics land.
+ * plan: enqueues the sorts and synchronises the stream ONCE.  counts [PINNED host] 2 int32, written by the last kernel:
+ * [0] error bits, [1] N_out.  A row outside the shape or a duplicate row fails the call (-1) and nothing is produced.
+ * fill: enqueue only, same stream, workspace and arguments, n_out = counts[1].  Writes every element of out_indices
+ * (n_out, 4) (not touched when subm), nbr (kvol, n_out): the input row of output o at offset k or -1, and nbr_t
+ * (kvol, n_in): the output row that reads input i at offset k or -1.                                                   */
+int64_t modest_spconv_rulebook_workspace_bytes(int64_t n_in, int kvol, int subm);
+int modest_spconv_rulebook_plan(const int32_t *indices_dev, int64_t n_in, int batch_size, const int32_t *shape3_host,
+                                const int32_t *kernel3_host, const int32_t *stride3_host, const int32_t *pad3_host, int subm,
+                                void *workspace_dev, int64_t workspace_bytes, int32_t *counts_pinned_host, void *stream);
+int modest_spconv_rulebook_fill(const int32_t *indices_dev, int64_t n_in, int batch_size, const int32_t *shape3_host,
+                                const int32_t *kernel3_host, const int32_t *stride3_host, const int32_t *pad3_host, int subm,
+                                const void *workspace_dev, int64_t workspace_bytes, int64_t n_out, int32_t *out_indices_dev,
+                                int32_t *nbr_dev, int32_t *nbr_t_dev, void *stream);
+/* out[r][n] = (((+0 + in[map[0][r]][0] * W_0[0][n]) + in[map[0][r]][1] * W_0[1][n]) + ...) over k ascending (rows with
+ * map[k][r] < 0 skipped), m ascending; product and sum rounded separately in float32, no fused multiply-add; then
+ * + bias[n] when bias is not NULL.  weight [dev] (kvol, w_cin, w_cout).  transposed == 0 (forward): in (n_in, w_cin),
+ * map = nbr, W_k[m][n] = weight[k][m][n], out (n_out, w_cout).  transposed != 0 (feature gradient): in = dy (n_in, w_cout),
+ * map = nbr_t, W_k[m][n] = weight[k][n][m], out (n_out, w_cin).  Channels 1 .. 128.  Writes every element of out; enqueue only. */
+int modest_spconv_gather_gemm(const float *in_dev, int64_t n_in, int in_channels, const float *weight_dev, int kvol, int w_cin,
+                              int w_cout, int transposed, const float *bias_dev, const int32_t *map_dev, int64_t n_out,
+                              float *out_dev, void *stream);
+/* dweight[k][ci][co] = sum over output rows o of x[nbr[k][o]][ci] * dy[o][co], dbias[co] = sum of dy[o][co] (dbias may be
+ * NULL).  The rows are cut into min(32, ceil(n_out / 1024)) segments, summed in ascending row order inside a segment and
+ * in ascending segment order after: the same bits on every run, no float atomics.  workspace [dev] 256-byte aligned,
+ * modest_spconv_wgrad_workspace_bytes bytes.  Enqueue only.                                                            */
+int64_t modest_spconv_wgrad_workspace_bytes(int64_t n_out, int kvol, int c_in, int c_out);
+int modest_spconv_wgrad(const float *x_dev, int64_t n_in, int c_in, const float *dy_dev, int64_t n_out, int c_out,
+                        const int32_t *nbr_dev, int kvol, void *workspace_dev, int64_t workspace_bytes, float *dweight_dev,
+                        float *dbias_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

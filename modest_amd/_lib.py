@@ -113,6 +113,15 @@ SIGNATURES = {
                                        VP]),
     "modest_voxelize_fill": (C.c_int, [VP, C.c_int64, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP, C.c_int64, C.c_int32,
                                        C.c_int64, VP, VP, VP, VP, VP]),
+    "modest_spconv_rulebook_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "modest_spconv_rulebook_plan": (C.c_int, [VP, C.c_int64, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int64, VP, VP]),
+    "modest_spconv_rulebook_fill": (C.c_int, [VP, C.c_int64, C.c_int, VP, VP, VP, VP, C.c_int, VP, C.c_int64, C.c_int64,
+                                              VP, VP, VP, VP]),
+    "modest_spconv_gather_gemm": (C.c_int, [VP, C.c_int64, C.c_int, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP,
+                                            C.c_int64, VP, VP]),
+    "modest_spconv_wgrad_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "modest_spconv_wgrad": (C.c_int, [VP, C.c_int64, C.c_int, VP, C.c_int64, C.c_int, VP, C.c_int, VP, C.c_int64, VP, VP,
+                                      VP]),
 }
 
 _lib = None

@@ -1142,3 +1142,176 @@ def voxelize(points: torch.Tensor, voxel_size, point_cloud_range, max_num_points
     pl = voxelize_plan(points, voxel_size, point_cloud_range, max_num_points, max_voxels, batch_size, workspace,
                        counts_pinned, geometry)
     return (*voxelize_fill(pl), pl.counts)
+
+
+# --------------------------------------------------------------------------- sparse 3-D convolutions (DESIGN.md section 7g)
+SPCONV_CALLS = {"rulebook": 0, "forward": 0, "input_grad": 0, "weight_grad": 0}   # library calls made, by kind
+
+
+def _triple(v, name: str):
+    if isinstance(v, (int, np.integer)):
+        return (int(v),) * 3
+    t = tuple(int(a) for a in v)
+    if len(t) != 3:
+        raise ValueError(f"{name} must be an int or three ints, got {v!r}")
+    return t
+
+
+def spconv_out_shape(spatial_shape, kernel, stride, padding, subm: bool = False):
+    """[D, H, W] of the output: the input's for a submanifold convolution, else (in + 2 p - k) // s + 1 per axis"""
+    shape, k, s, p = (_triple(v, n) for v, n in ((spatial_shape, "spatial_shape"), (kernel, "kernel_size"),
+                                                  (stride, "stride"), (padding, "padding")))
+    if min(shape) < 1 or min(k) < 1:
+        raise ValueError(f"spatial shape {list(shape)} and kernel {list(k)} must be positive")
+    if subm:
+        if any(a % 2 == 0 for a in k):
+            raise ValueError(f"a submanifold convolution needs odd kernel sizes, got {list(k)}")
+        return list(shape)
+    if min(s) < 1 or min(p) < 0:
+        raise ValueError(f"stride {list(s)} must be positive and padding {list(p)} non-negative")
+    out = [(shape[j] + 2 * p[j] - k[j]) // s[j] + 1 for j in range(3)]
+    if min(out) <= 0:
+        raise ValueError(f"output shape {out} of input {list(shape)}, kernel {list(k)}, stride {list(s)}, padding {list(p)}")
+    return out
+
+
+class SpconvRulebook:
+    """what one geometry on one set of sites needs: .out_indices (N_out, 4) int32 (the input's own tensor when subm),
+    .out_shape, .nbr (K, N_out) / .nbr_t (K, N_in) int32 with -1 for an absent neighbour, and the geometry it was built for"""
+
+    def same_geometry(self, batch_size, spatial_shape, kernel, stride, padding, subm) -> bool:
+        want = (int(batch_size), _triple(spatial_shape, "spatial_shape"), _triple(kernel, "kernel_size"), bool(subm))
+        if not subm:
+            want += (_triple(stride, "stride"), _triple(padding, "padding"))
+        return self.geometry == want
+
+
+def spconv_rulebook(indices: torch.Tensor, batch_size: int, spatial_shape, kernel, stride=1, padding=0, subm: bool = False,
+                    workspace: Optional[torch.Tensor] = None, counts_pinned: Optional[torch.Tensor] = None) -> SpconvRulebook:
+    """Output sites and neighbour maps of a sparse convolution on PyTorch's current stream; ONE stream synchronise (the
+    output count sizes the maps, and a duplicate or out-of-range row must be reported before anything is produced)."""
+    _dev(indices, torch.int32, "indices")
+    if indices.ndim != 2 or indices.shape[1] != 4:
+        raise ValueError(f"indices has shape {tuple(indices.shape)}, expected (N, 4) [b, z, y, x]")
+    rb = SpconvRulebook()
+    rb.subm = bool(subm)
+    rb.batch_size = int(batch_size)
+    rb.in_shape = list(_triple(spatial_shape, "spatial_shape"))
+    rb.kernel, rb.stride, rb.padding = (_triple(v, n) for v, n in ((kernel, "kernel_size"), (stride, "stride"), (padding, "padding")))
+    rb.out_shape = spconv_out_shape(rb.in_shape, rb.kernel, rb.stride, rb.padding, rb.subm)
+    rb.geometry = (rb.batch_size, tuple(rb.in_shape), rb.kernel, rb.subm) + (() if rb.subm else (rb.stride, rb.padding))
+    rb.kvol = rb.kernel[0] * rb.kernel[1] * rb.kernel[2]
+    rb.indices, rb.n_in = indices, int(indices.shape[0])
+    dev = indices.device
+    lib = load()
+    geo = [np.ascontiguousarray(v, dtype=np.int32) for v in (rb.in_shape, rb.kernel, rb.stride, rb.padding)]
+    nbytes = int(lib.modest_spconv_rulebook_workspace_bytes(rb.n_in, rb.kvol, int(rb.subm)))
+    if nbytes < 0:
+        check(nbytes, "modest_spconv_rulebook_workspace_bytes")
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    if counts_pinned is None:
+        counts_pinned = torch.zeros((2,), dtype=torch.int32).pin_memory()
+    if counts_pinned.dtype != torch.int32 or not counts_pinned.is_pinned() or counts_pinned.numel() < 2:
+        raise ValueError("counts_pinned must be a pinned int32 host tensor of two words")
+    SPCONV_CALLS["rulebook"] += 1
+    with torch.cuda.device(dev):
+        check(lib.modest_spconv_rulebook_plan(indices.data_ptr(), rb.n_in, rb.batch_size, *(_np_ptr(g) for g in geo),
+                                              int(rb.subm), workspace.data_ptr(), workspace.numel(), counts_pinned.data_ptr(),
+                                              _stream()), "modest_spconv_rulebook_plan")
+        rb.n_out = int(counts_pinned[1]) if not rb.subm else rb.n_in
+        rb.out_indices = indices if rb.subm else torch.empty((rb.n_out, 4), dtype=torch.int32, device=dev)
+        rb.nbr = torch.empty((rb.kvol, rb.n_out), dtype=torch.int32, device=dev)
+        rb.nbr_t = torch.empty((rb.kvol, rb.n_in), dtype=torch.int32, device=dev)
+        check(lib.modest_spconv_rulebook_fill(indices.data_ptr(), rb.n_in, rb.batch_size, *(_np_ptr(g) for g in geo),
+                                              int(rb.subm), workspace.data_ptr(), workspace.numel(), rb.n_out,
+                                              rb.out_indices.data_ptr(), rb.nbr.data_ptr(), rb.nbr_t.data_ptr(), _stream()),
+              "modest_spconv_rulebook_fill")
+    rb.workspace = workspace   # (the fill kernels read it: it must outlive them on this stream)
+    return rb
+
+
+def _spconv_weight(weight: torch.Tensor, rb: SpconvRulebook):
+    _dev(weight, torch.float32, "weight")
+    if weight.ndim == 5:
+        if tuple(weight.shape[:3]) != tuple(rb.kernel):
+            raise ValueError(f"weight has kernel {tuple(weight.shape[:3])}, the rulebook {tuple(rb.kernel)}")
+    elif weight.ndim != 3 or weight.shape[0] != rb.kvol:
+        raise ValueError(f"weight has shape {tuple(weight.shape)}, expected (kz, ky, kx, Cin, Cout) or (K, Cin, Cout)")
+    cin, cout = int(weight.shape[-2]), int(weight.shape[-1])
+    if not (1 <= cin <= 128 and 1 <= cout <= 128):
+        raise ValueError("channels must lie in 1 .. 128")
+    return cin, cout
+
+
+def spconv_forward(features: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rb: SpconvRulebook,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """features (N_in, Cin), weight (kz, ky, kx, Cin, Cout) or (K, Cin, Cout), bias (Cout,) or None -> (N_out, Cout), every
+    element written, in the fixed order of DESIGN.md section 7g.  Enqueue only."""
+    cin, cout = _spconv_weight(weight, rb)
+    _dev(features, torch.float32, "features")
+    if tuple(features.shape) != (rb.n_in, cin):
+        raise ValueError(f"features has shape {tuple(features.shape)}, expected {(rb.n_in, cin)}")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (cout,):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected {(cout,)}")
+    if out is None:
+        out = torch.empty((rb.n_out, cout), dtype=torch.float32, device=features.device)
+    _dev(out, torch.float32, "out")
+    if tuple(out.shape) != (rb.n_out, cout):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(rb.n_out, cout)}")
+    SPCONV_CALLS["forward"] += 1
+    with torch.cuda.device(features.device):
+        check(load().modest_spconv_gather_gemm(features.data_ptr(), rb.n_in, cin, weight.data_ptr(), rb.kvol, cin, cout, 0,
+                                               bias.data_ptr() if bias is not None else None, rb.nbr.data_ptr(), rb.n_out,
+                                               out.data_ptr(), _stream()), "modest_spconv_gather_gemm")
+    return out
+
+
+def spconv_backward(features: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, rb: SpconvRulebook,
+                    need_input_grad: bool = True, need_weight_grad: bool = True, need_bias_grad: bool = True,
+                    grad_input: Optional[torch.Tensor] = None, grad_weight: Optional[torch.Tensor] = None,
+                    grad_bias: Optional[torch.Tensor] = None):
+    """-> (grad_input (N_in, Cin) | None, grad_weight (shape of weight) | None, grad_bias (Cout,) | None).  A gradient
+    that is not needed launches nothing.  Enqueue only."""
+    cin, cout = _spconv_weight(weight, rb)
+    _dev(features, torch.float32, "features")
+    _dev(grad_out, torch.float32, "grad_out")
+    if tuple(features.shape) != (rb.n_in, cin) or tuple(grad_out.shape) != (rb.n_out, cout):
+        raise ValueError(f"features {tuple(features.shape)} / grad_out {tuple(grad_out.shape)}, expected "
+                         f"{(rb.n_in, cin)} / {(rb.n_out, cout)}")
+    dev = features.device
+    lib = load()
+
+    def given(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        _dev(t, torch.float32, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    dx = dw = db = None
+    with torch.cuda.device(dev):
+        if need_input_grad:
+            dx = given(grad_input, (rb.n_in, cin), "grad_input")
+            SPCONV_CALLS["input_grad"] += 1
+            check(lib.modest_spconv_gather_gemm(grad_out.data_ptr(), rb.n_out, cout, weight.data_ptr(), rb.kvol, cin, cout, 1,
+                                                None, rb.nbr_t.data_ptr(), rb.n_in, dx.data_ptr(), _stream()),
+                  "modest_spconv_gather_gemm")
+        if need_weight_grad or need_bias_grad:
+            dw = given(grad_weight, tuple(weight.shape), "grad_weight")
+            if need_bias_grad:
+                db = given(grad_bias, (cout,), "grad_bias")
+            nbytes = int(lib.modest_spconv_wgrad_workspace_bytes(rb.n_out, rb.kvol, cin, cout))
+            if nbytes < 0:
+                check(nbytes, "modest_spconv_wgrad_workspace_bytes")
+            ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+            SPCONV_CALLS["weight_grad"] += 1
+            check(lib.modest_spconv_wgrad(features.data_ptr(), rb.n_in, cin, grad_out.data_ptr(), rb.n_out, cout,
+                                          rb.nbr.data_ptr(), rb.kvol, ws.data_ptr(), ws.numel(), dw.data_ptr(),
+                                          db.data_ptr() if db is not None else None, _stream()), "modest_spconv_wgrad")
+            if not need_weight_grad:
+                dw = None
+    return dx, dw, db

@@ -9,6 +9,9 @@ calls.  The ``spconv`` stand-in carries one real part, ``spconv.utils`` with the
 data pipeline constructs (``modest_amd.utils.spconv_utils``); an installed spconv is left alone.  Any other attribute of
 a stand-in is a class that can be named and subclassed at import time and raises ``NotImplementedError`` when it is called.  Calling ``install`` again changes nothing.  Nothing here touches the GPU:
 the shims open the library at their first call.
+
+``install(sparse_conv=True)`` binds ``modest_amd.utils.spconv`` -- the sparse 3-D convolutions SECOND's backbone is built
+from -- as ``spconv`` instead of the stand-in; ``spconv.utils`` is the same module either way.
 """
 import importlib
 import importlib.util
@@ -26,6 +29,7 @@ SHIMS = {
 }
 STAND_INS = ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda", "spconv")
 SPCONV_UTILS = "modest_amd.utils.spconv_utils"   # bound as spconv.utils while spconv itself is a stand-in
+SPCONV = "modest_amd.utils.spconv"               # bound as spconv by install(sparse_conv=True)
 
 
 class StandIn(types.ModuleType):
@@ -44,11 +48,28 @@ class StandIn(types.ModuleType):
         return missing
 
 
-def install(stand_ins=True):
+def _bind_sparse_conv():
+    """spconv := modest_amd.utils.spconv unless a real spconv is imported or installed -> the module bound, or None"""
+    ours = importlib.import_module(SPCONV)
+    mod = sys.modules.get("spconv")
+    if mod is None and importlib.util.find_spec("spconv") is not None:
+        return None   # the real package is installed: leave it alone
+    if mod is not None and mod is not ours and not isinstance(mod, StandIn):
+        return None   # ... or already imported
+    sys.modules["spconv"] = ours
+    sys.modules["spconv.utils"] = ours.utils
+    return ours
+
+
+def install(stand_ins=True, sparse_conv=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     for name, target in SHIMS.items():
         bound[name] = sys.modules[name] = importlib.import_module(target)
+    if sparse_conv:
+        ours = _bind_sparse_conv()
+        if ours is not None and not stand_ins:
+            bound["spconv"] = ours
     if stand_ins:
         for name in STAND_INS:
             mod = sys.modules.get(name)
