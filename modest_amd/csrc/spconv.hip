@@ -6,7 +6,7 @@
 //
 // Rulebook.  A site (b, z, y, x) becomes the 64-bit key ((b * D + z) * H + y) * W + x; no table over the grid exists.
 //   1. keys of the input rows (a row outside the shape sets an error bit), stable LSD radix sort of (key, row) over the
-//      bits in use, equal neighbours in the sorted keys set the duplicate bit.
+//      bits in use (sort64.hip), equal neighbours in the sorted keys set the duplicate bit.
 //   2. strided only: the candidate output key of every (input, offset) -- o = (i + p - k) / s where that is an integer
 //      inside the output shape, the sentinel `cells` otherwise --, sorted; the first of every run of equal keys is an
 //      output site, its rank in an exclusive scan its row: rows come out ascending in (b, z, y, x).
@@ -25,15 +25,14 @@
 
 #include "common.h"
 #include "modest_hip.h"
+#include "sort64.h"
 
 namespace {
 
 constexpr int64_t SP_MAX_ROWS = 2147483647 - 4096;
 constexpr int SP_KSIZE_MAX = 7;
 constexpr int SP_CH_MAX = 128;
-constexpr int SP_SORT_T = 256, SP_SORT_ITEMS = 8, SP_SORT_WAVES = SP_SORT_T / 64;
-constexpr int SP_TILE = SP_SORT_T * SP_SORT_ITEMS;
-constexpr int SP_SCAN_T = 1024;
+constexpr int SP_SCAN_T = 1024;   // rows per block of the head scan
 constexpr int SP_HDR_WORDS = 64;   // [0] error bits
 constexpr int SP_ERR_RANGE = 1, SP_ERR_DUP = 2;
 
@@ -44,7 +43,7 @@ struct SpGeom {
 };
 
 struct SpLayout {
-    int64_t m, sort_tiles, flag_blocks;
+    int64_t m, flag_blocks;
     size_t hdr, key_a, key_b, idx_a, idx_b, table, in_keys, in_idx, rank, bsum, bytes;
 };
 
@@ -52,7 +51,6 @@ struct SpLayout {
 inline SpLayout sp_layout(int64_t n_in, int kvol, int subm) {
     SpLayout L;
     L.m = subm ? n_in : n_in * kvol;   // rows of the larger of the two sorts
-    L.sort_tiles = (L.m + SP_TILE - 1) / SP_TILE;
     L.flag_blocks = (L.m + SP_SCAN_T - 1) / SP_SCAN_T;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -65,22 +63,13 @@ inline SpLayout sp_layout(int64_t n_in, int kvol, int subm) {
     L.key_b = take(sizeof(uint64_t) * (size_t)L.m);
     L.idx_a = take(sizeof(uint32_t) * (size_t)n_in);
     L.idx_b = take(sizeof(uint32_t) * (size_t)n_in);
-    L.table = take(sizeof(uint32_t) * (256 * (size_t)L.sort_tiles + 1));
+    L.table = take(sizeof(uint32_t) * sort64_table_words(L.m));
     L.in_keys = take(sizeof(uint64_t) * (size_t)n_in);
     L.in_idx = take(sizeof(uint32_t) * (size_t)n_in);
     L.rank = take(sizeof(int32_t) * (size_t)L.m);
     L.bsum = take(sizeof(uint32_t) * ((size_t)L.flag_blocks + 1));
     L.bytes = off;
     return L;
-}
-
-inline int sp_bit_length(uint64_t v) {
-    int b = 0;
-    while (v) {
-        ++b;
-        v >>= 1;
-    }
-    return b;
 }
 
 // checks the geometry and fills g; the products are formed in steps that cannot overflow 64 bits
@@ -170,129 +159,6 @@ __global__ __launch_bounds__(256) void sp_candidates(const int32_t *__restrict__
     cand[e] = ok ? (uint64_t)((((int64_t)b * g.out[0] + o[0]) * g.out[1] + o[1]) * g.out[2] + o[2]) : (uint64_t)g.cells_out;
 }
 
-// ---------------------------------------------------------------- the sort ----------------------------------------------
-// Stable LSD radix sort, 8 bits per pass: digit counts per tile, one exclusive scan of the digit-major (digit, tile)
-// table, and a scatter whose ranks inside a tile come from ballots and per-wavefront running counts (the scheme of
-// voxelize.hip; kept as a separate copy under its own names because the build's resource table is keyed by kernel name).
-__global__ __launch_bounds__(SP_SORT_T) void sp_sort_count(const uint64_t *__restrict__ keys, int n, int shift,
-                                                           uint32_t *__restrict__ table, int64_t tiles) {
-    __shared__ unsigned h[256];
-    const int tid = threadIdx.x;
-    h[tid] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * SP_TILE;
-#pragma unroll
-    for (int u = 0; u < SP_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * SP_SORT_T + tid;
-        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    table[(int64_t)tid * tiles + blockIdx.x] = h[tid];
-}
-
-// exclusive scan in place of t[0 .. entries), the total in t[entries]; one workgroup
-__global__ __launch_bounds__(SP_SCAN_T) void sp_scan(uint32_t *__restrict__ t, int64_t entries) {
-    __shared__ unsigned ws[SP_SCAN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned carry = 0;
-    for (int64_t t0 = 0; t0 < entries; t0 += SP_SCAN_T) {
-        const int64_t i = t0 + tid;
-        const unsigned v = i < entries ? t[i] : 0u;
-        unsigned inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        if (lane == 63) ws[w] = inc;
-        __syncthreads();
-        unsigned before = 0, total = 0;
-        for (int q = 0; q < SP_SCAN_T / 64; ++q) {
-            if (q < w) before += ws[q];
-            total += ws[q];
-        }
-        if (i < entries) t[i] = carry + before + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) t[entries] = carry;
-}
-
-// idx_in == nullptr: keys only
-__global__ __launch_bounds__(SP_SORT_T) void sp_sort_scatter(const uint64_t *__restrict__ keys_in,
-                                                             const uint32_t *__restrict__ idx_in,
-                                                             uint64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out,
-                                                             int n, int shift, const uint32_t *__restrict__ table,
-                                                             int64_t tiles) {
-    __shared__ unsigned wh[SP_SORT_WAVES][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int q = 0; q < SP_SORT_WAVES; ++q) wh[q][tid] = 0;
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int64_t base = (int64_t)blockIdx.x * SP_TILE + (int64_t)w * (64 * SP_SORT_ITEMS);
-    uint64_t key[SP_SORT_ITEMS];
-    uint32_t id[SP_SORT_ITEMS];
-    unsigned rank[SP_SORT_ITEMS];
-#pragma unroll
-    for (int u = 0; u < SP_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * 64 + lane;
-        const bool valid = i < n;
-        key[u] = valid ? keys_in[i] : 0ull;
-        id[u] = (valid && idx_in) ? idx_in[i] : 0u;
-        const unsigned d = (unsigned)(key[u] >> shift) & 255u;
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool one = (d >> bit) & 1u;
-            const unsigned long long bal = __ballot(one);
-            same &= one ? bal : ~bal;
-        }
-        // only this wavefront touches wh[w]: its lanes read before the group's first lane writes (program order)
-        const unsigned prev = wh[w][d];
-        rank[u] = prev + __popcll(same & below);
-        __builtin_amdgcn_wave_barrier();
-        if (valid && (same & below) == 0ull) wh[w][d] = prev + __popcll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {
-        unsigned run = table[(int64_t)tid * tiles + blockIdx.x];
-#pragma unroll
-        for (int q = 0; q < SP_SORT_WAVES; ++q) {
-            const unsigned cnt = wh[q][tid];
-            wh[q][tid] = run;
-            run += cnt;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < SP_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * 64 + lane;
-        if (i < n) {
-            const unsigned d = (unsigned)(key[u] >> shift) & 255u;
-            const unsigned pos = wh[w][d] + rank[u];
-            if (pos < (unsigned)n) {   // (always: the table counts exactly these rows)
-                keys_out[pos] = key[u];
-                if (idx_in) idx_out[pos] = id[u];
-            }
-        }
-    }
-}
-
-// sorts (key, idx) over `bits` bits between the two buffers; returns the index of the buffer that holds the result
-int sp_sort(uint64_t *key[2], uint32_t *idx[2], bool with_idx, int n, int bits, uint32_t *table, hipStream_t st) {
-    const int64_t tiles = ((int64_t)n + SP_TILE - 1) / SP_TILE;
-    const int passes = (bits + 7) / 8;
-    for (int ps = 0; ps < passes; ++ps) {
-        const int in = ps & 1, out = in ^ 1;
-        sp_sort_count<<<(unsigned)tiles, SP_SORT_T, 0, st>>>(key[in], n, 8 * ps, table, tiles);
-        sp_scan<<<1, SP_SCAN_T, 0, st>>>(table, 256 * tiles);
-        sp_sort_scatter<<<(unsigned)tiles, SP_SORT_T, 0, st>>>(key[in], with_idx ? idx[in] : nullptr, key[out],
-                                                               with_idx ? idx[out] : nullptr, n, 8 * ps, table, tiles);
-    }
-    return passes & 1;
-}
-
 // ---------------------------------------------------------------- output sites ------------------------------------------
 __device__ __forceinline__ bool sp_is_head(const uint64_t *__restrict__ sk, int64_t p, uint64_t sentinel) {
     const uint64_t key = sk[p];
@@ -310,15 +176,9 @@ __global__ __launch_bounds__(SP_SCAN_T) void sp_head_sums(const uint64_t *__rest
 __global__ __launch_bounds__(SP_SCAN_T) void sp_head_ranks(const uint64_t *__restrict__ sk, int m, uint64_t sentinel,
                                                            const uint32_t *__restrict__ bsum, uint64_t *__restrict__ out_keys) {
     __shared__ unsigned ws[SP_SCAN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t p = (int64_t)blockIdx.x * SP_SCAN_T + tid;
+    const int64_t p = (int64_t)blockIdx.x * SP_SCAN_T + threadIdx.x;
     const bool f = p < m && sp_is_head(sk, p, sentinel);
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) ws[w] = __popcll(bal);
-    __syncthreads();
-    unsigned before = bsum[blockIdx.x];
-    for (int q = 0; q < w; ++q) before += ws[q];
-    const unsigned r = before + __popcll(bal & ((1ull << lane) - 1ull));
+    const unsigned r = sort64_block_rank(f, bsum + blockIdx.x, ws);
     if (f && r < (unsigned)m) out_keys[r] = sk[p];
 }
 
@@ -653,7 +513,7 @@ extern "C" int modest_spconv_rulebook_plan(const int32_t *indices_dev, int64_t n
     const unsigned row_blocks = (unsigned)((n_in + 255) / 256);
     MODEST_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(int32_t) * SP_HDR_WORDS, st));
     sp_in_keys<<<row_blocks, 256, 0, st>>>(indices_dev, n, g, key[0], idx[0], hdr);
-    const int fin = sp_sort(key, idx, true, n, sp_bit_length((uint64_t)g.cells_in), table, st);
+    const int fin = sort64(key, idx, n, sort64_bit_length((uint64_t)g.cells_in), table, st);
     MODEST_HIP_CHECK(hipMemcpyAsync(in_keys, key[fin], sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
     MODEST_HIP_CHECK(hipMemcpyAsync(in_idx, idx[fin], sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
     sp_dup_check<<<row_blocks, 256, 0, st>>>(in_keys, n, (uint64_t)g.cells_in, hdr);
@@ -662,9 +522,9 @@ extern "C" int modest_spconv_rulebook_plan(const int32_t *indices_dev, int64_t n
     } else {
         const int m = (int)L.m;
         sp_candidates<<<(unsigned)((L.m + 255) / 256), 256, 0, st>>>(indices_dev, L.m, g, key[0]);
-        const int cf = sp_sort(key, idx, false, m, sp_bit_length((uint64_t)g.cells_out), table, st);
+        const int cf = sort64(key, nullptr, m, sort64_bit_length((uint64_t)g.cells_out), table, st);
         sp_head_sums<<<(unsigned)L.flag_blocks, SP_SCAN_T, 0, st>>>(key[cf], m, (uint64_t)g.cells_out, bsum);
-        sp_scan<<<1, SP_SCAN_T, 0, st>>>(bsum, L.flag_blocks);
+        sort64_scan(bsum, L.flag_blocks, st);
         // the output keys land in the sort's other buffer: ascending, unique, N_out of them
         sp_head_ranks<<<(unsigned)L.flag_blocks, SP_SCAN_T, 0, st>>>(key[cf], m, (uint64_t)g.cells_out, bsum, key[cf ^ 1]);
         sp_finish<<<1, 64, 0, st>>>(hdr, bsum + L.flag_blocks, 0, counts_pinned_host);
@@ -695,7 +555,7 @@ extern "C" int modest_spconv_rulebook_fill(const int32_t *indices_dev, int64_t n
     const uint64_t *in_keys = reinterpret_cast<const uint64_t *>(ws + L.in_keys);
     const uint32_t *in_idx = reinterpret_cast<const uint32_t *>(ws + L.in_idx);
     // where plan left the output keys: the buffer the candidate sort did not end in
-    const int cf = ((sp_bit_length((uint64_t)g.cells_out) + 7) / 8) & 1;
+    const int cf = sort64_result(sort64_bit_length((uint64_t)g.cells_out));
     const uint64_t *out_keys = g.subm ? nullptr : reinterpret_cast<const uint64_t *>(ws + (cf ? L.key_a : L.key_b));
     const int ni = (int)n_in, no = (int)n_out;
     if (!g.subm) sp_out_indices<<<(unsigned)((n_out + 255) / 256), 256, 0, st>>>(out_keys, no, g, out_indices_dev);

@@ -12,10 +12,7 @@
 // The device path has no table over the grid and nothing in it depends on the order in which atomics land:
 //   1. key(i) = (b << bits_cell) | cell, or (batch_cap << bits_cell) for a dropped point; the same kernel finds the first
 //      row of every cloud and reports a batch column that is not a non-decreasing sequence of integers in [0, batch_cap).
-//   2. stable LSD radix sort of (key, i), 8 bits per pass over the bits in use only.  Per pass: digit counts per tile
-//      (LDS counters: a count does not depend on arrival order), one exclusive scan of the digit-major (digit, tile)
-//      table, and a scatter whose ranks inside a tile come from ballots (the lanes of a 64-row sub-block that share a
-//      digit) and per-wavefront running counts -- every wavefront walks its own contiguous part of the tile in order.
+//   2. stable LSD radix sort of (key, i), 8 bits per pass over the bits in use only (sort64.hip has the scheme).
 //   3. the first row of a run of equal keys is the cell's first point (the sort is stable): flag[i] = 1 there.
 //   4. exclusive scan of the flags in ROW order = the number of cells opened before row i.  Taken at a cell's first point
 //      it is the cell's voxel number over the batch, minus the value at the cloud's first row the number within the cloud;
@@ -28,15 +25,14 @@
 
 #include "common.h"
 #include "modest_hip.h"
+#include "sort64.h"
 
 namespace {
 
 constexpr int64_t VX_MAX_CELLS = 2147483647;
 constexpr int64_t VX_MAX_ROWS = 2147483647 - 4096;
 constexpr int VX_BATCH_MAX = 4096;
-constexpr int VX_SORT_T = 256, VX_SORT_ITEMS = 8, VX_SORT_WAVES = VX_SORT_T / 64;
-constexpr int VX_TILE = VX_SORT_T * VX_SORT_ITEMS;   // rows per sort tile; a wavefront owns 64 * VX_SORT_ITEMS consecutive ones
-constexpr int VX_SCAN_T = 1024;
+constexpr int VX_SCAN_T = 1024;   // rows per block of the flag scan
 constexpr int VX_HDR_WORDS = 64;   // [0] error bits, [1] clouds seen (last batch index + 1)
 constexpr int VX_ERR_ORDER = 1, VX_ERR_BATCH = 2;
 constexpr int VX_FILL_T = 256;
@@ -48,13 +44,12 @@ struct VxGeom {
 
 // the carve of the workspace: a function of the row count and the batch capacity, never of the grid
 struct VxLayout {
-    int64_t sort_tiles, flag_blocks;
+    int64_t flag_blocks;
     size_t hdr, start, rbase, obase, key_a, key_b, idx_a, idx_b, table, rank, bsum, headpos, bytes;
 };
 
 inline VxLayout vx_layout(int64_t n, int batch_cap) {
     VxLayout L;
-    L.sort_tiles = (n + VX_TILE - 1) / VX_TILE;
     L.flag_blocks = (n + VX_SCAN_T - 1) / VX_SCAN_T;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -70,7 +65,7 @@ inline VxLayout vx_layout(int64_t n, int batch_cap) {
     L.key_b = take(sizeof(uint64_t) * (size_t)n);
     L.idx_a = take(sizeof(uint32_t) * (size_t)n);
     L.idx_b = take(sizeof(uint32_t) * (size_t)n);
-    L.table = take(sizeof(uint32_t) * (256 * (size_t)L.sort_tiles + 1));
+    L.table = take(sizeof(uint32_t) * sort64_table_words(n));
     L.rank = take(sizeof(int32_t) * (size_t)n);
     L.bsum = take(sizeof(uint32_t) * ((size_t)L.flag_blocks + 1));
     L.headpos = take(sizeof(int32_t) * (size_t)n);
@@ -78,24 +73,14 @@ inline VxLayout vx_layout(int64_t n, int batch_cap) {
     return L;
 }
 
-inline int vx_bit_length(uint64_t v) {
-    int b = 0;
-    while (v) {
-        ++b;
-        v >>= 1;
-    }
-    return b;
-}
-
-// bits of a cell number, bits of the whole key ((batch_cap << bits_cell) is the key of a dropped point), sort passes
+// bits of a cell number, bits of the whole key ((batch_cap << bits_cell) is the key of a dropped point)
 struct VxBits {
-    int cell, all, passes;
+    int cell, all;
 };
 inline VxBits vx_bits(int64_t cells, int batch_cap) {
     VxBits b;
-    b.cell = vx_bit_length((uint64_t)(cells - 1));
-    b.all = b.cell + vx_bit_length((uint64_t)batch_cap);
-    b.passes = (b.all + 7) / 8;
+    b.cell = sort64_bit_length((uint64_t)(cells - 1));
+    b.all = b.cell + sort64_bit_length((uint64_t)batch_cap);
     return b;
 }
 
@@ -162,111 +147,6 @@ __global__ __launch_bounds__(256) void vx_keys(const float *__restrict__ pts, in
     idx[i] = (uint32_t)i;
 }
 
-// ---------------------------------------------------------------- 2. the sort ------------------------------------------
-__global__ __launch_bounds__(VX_SORT_T) void vx_sort_count(const uint64_t *__restrict__ keys, int n, int shift,
-                                                           uint32_t *__restrict__ table, int64_t tiles) {
-    __shared__ unsigned h[256];
-    const int tid = threadIdx.x;
-    h[tid] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * VX_TILE;
-#pragma unroll
-    for (int u = 0; u < VX_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * VX_SORT_T + tid;
-        if (i < n) atomicAdd(&h[(unsigned)(keys[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    table[(int64_t)tid * tiles + blockIdx.x] = h[tid];
-}
-
-// exclusive scan in place of t[0 .. entries), the total in t[entries]; one workgroup
-__global__ __launch_bounds__(VX_SCAN_T) void vx_scan(uint32_t *__restrict__ t, int64_t entries) {
-    __shared__ unsigned ws[VX_SCAN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned carry = 0;
-    for (int64_t t0 = 0; t0 < entries; t0 += VX_SCAN_T) {
-        const int64_t i = t0 + tid;
-        const unsigned v = i < entries ? t[i] : 0u;
-        unsigned inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        if (lane == 63) ws[w] = inc;
-        __syncthreads();
-        unsigned before = 0, total = 0;
-        for (int q = 0; q < VX_SCAN_T / 64; ++q) {
-            if (q < w) before += ws[q];
-            total += ws[q];
-        }
-        if (i < entries) t[i] = carry + before + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) t[entries] = carry;
-}
-
-__global__ __launch_bounds__(VX_SORT_T) void vx_sort_scatter(const uint64_t *__restrict__ keys_in,
-                                                             const uint32_t *__restrict__ idx_in,
-                                                             uint64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out,
-                                                             int n, int shift, const uint32_t *__restrict__ table,
-                                                             int64_t tiles) {
-    __shared__ unsigned wh[VX_SORT_WAVES][256];   // running count per wavefront and digit, then the wavefront's base
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int q = 0; q < VX_SORT_WAVES; ++q) wh[q][tid] = 0;
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int64_t base = (int64_t)blockIdx.x * VX_TILE + (int64_t)w * (64 * VX_SORT_ITEMS);
-    uint64_t key[VX_SORT_ITEMS];
-    uint32_t id[VX_SORT_ITEMS];
-    unsigned rank[VX_SORT_ITEMS];
-#pragma unroll
-    for (int u = 0; u < VX_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * 64 + lane;
-        const bool valid = i < n;
-        key[u] = valid ? keys_in[i] : 0ull;
-        id[u] = valid ? idx_in[i] : 0u;
-        const unsigned d = (unsigned)(key[u] >> shift) & 255u;
-        unsigned long long same = __ballot(valid);   // the lanes of this sub-block with my digit
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool one = (d >> bit) & 1u;
-            const unsigned long long bal = __ballot(one);
-            same &= one ? bal : ~bal;
-        }
-        // only this wavefront touches wh[w]: its lanes read before the group's first lane writes (program order)
-        const unsigned prev = wh[w][d];
-        rank[u] = prev + __popcll(same & below);
-        __builtin_amdgcn_wave_barrier();
-        if (valid && (same & below) == 0ull) wh[w][d] = prev + __popcll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {   // thread d: where digit d of this tile starts, then of each wavefront's part
-        unsigned run = table[(int64_t)tid * tiles + blockIdx.x];
-#pragma unroll
-        for (int q = 0; q < VX_SORT_WAVES; ++q) {
-            const unsigned cnt = wh[q][tid];
-            wh[q][tid] = run;
-            run += cnt;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < VX_SORT_ITEMS; ++u) {
-        const int64_t i = base + u * 64 + lane;
-        if (i < n) {
-            const unsigned d = (unsigned)(key[u] >> shift) & 255u;
-            const unsigned pos = wh[w][d] + rank[u];
-            if (pos < (unsigned)n) {   // (always: the table counts exactly these rows)
-                keys_out[pos] = key[u];
-                idx_out[pos] = id[u];
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------- 3./4. first points, voxel numbers --------------------
 __device__ __forceinline__ bool vx_is_head(const uint64_t *__restrict__ sk, int64_t p, int batch_cap, int bits_cell) {
     const uint64_t key = sk[p];
@@ -291,15 +171,9 @@ __global__ __launch_bounds__(VX_SCAN_T) void vx_flag_sums(const int32_t *__restr
 // flag -> exclusive rank, in place (a thread reads its own word before the barrier and writes it after)
 __global__ __launch_bounds__(VX_SCAN_T) void vx_ranks(int32_t *__restrict__ flag_rank, int n, const uint32_t *__restrict__ bsum) {
     __shared__ unsigned ws[VX_SCAN_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t i = (int64_t)blockIdx.x * VX_SCAN_T + tid;
-    const bool f = i < n && flag_rank[i] != 0;
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) ws[w] = __popcll(bal);
-    __syncthreads();
-    unsigned before = bsum[blockIdx.x];
-    for (int q = 0; q < w; ++q) before += ws[q];
-    if (i < n) flag_rank[i] = (int32_t)(before + __popcll(bal & ((1ull << lane) - 1ull)));
+    const int64_t i = (int64_t)blockIdx.x * VX_SCAN_T + threadIdx.x;
+    const unsigned r = sort64_block_rank(i < n && flag_rank[i] != 0, bsum + blockIdx.x, ws);
+    if (i < n) flag_rank[i] = (int32_t)r;
 }
 
 __global__ __launch_bounds__(256) void vx_headpos(const uint64_t *__restrict__ sk, const uint32_t *__restrict__ si, int n,
@@ -446,17 +320,10 @@ extern "C" int modest_voxelize_plan(const float *points_dev, int64_t n_rows, int
     const unsigned row_blocks = (unsigned)((n_rows + 255) / 256);
     MODEST_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(int32_t) * VX_HDR_WORDS, st));
     vx_keys<<<row_blocks, 256, 0, st>>>(points_dev, n, 1 + c, g, batch_cap, bits.cell, key[0], idx[0], start, hdr);
-    for (int ps = 0; ps < bits.passes; ++ps) {
-        const int in = ps & 1, out = in ^ 1;
-        vx_sort_count<<<(unsigned)L.sort_tiles, VX_SORT_T, 0, st>>>(key[in], n, 8 * ps, table, L.sort_tiles);
-        vx_scan<<<1, VX_SCAN_T, 0, st>>>(table, 256 * L.sort_tiles);
-        vx_sort_scatter<<<(unsigned)L.sort_tiles, VX_SORT_T, 0, st>>>(key[in], idx[in], key[out], idx[out], n, 8 * ps, table,
-                                                                      L.sort_tiles);
-    }
-    const int fin = bits.passes & 1;
+    const int fin = sort64(key, idx, n, bits.all, table, st);
     vx_flags<<<row_blocks, 256, 0, st>>>(key[fin], idx[fin], n, batch_cap, bits.cell, rank);
     vx_flag_sums<<<(unsigned)L.flag_blocks, VX_SCAN_T, 0, st>>>(rank, n, bsum);
-    vx_scan<<<1, VX_SCAN_T, 0, st>>>(bsum, L.flag_blocks);
+    sort64_scan(bsum, L.flag_blocks, st);
     vx_ranks<<<(unsigned)L.flag_blocks, VX_SCAN_T, 0, st>>>(rank, n, bsum);
     vx_headpos<<<row_blocks, 256, 0, st>>>(key[fin], idx[fin], n, batch_cap, bits.cell, rank, headpos);
     vx_plan<<<1, 256, 0, st>>>(start, rank, bsum + L.flag_blocks, n, batch_cap, max_voxels, rbase, obase, hdr, counts_pinned_host);
@@ -487,7 +354,7 @@ extern "C" int modest_voxelize_fill(const float *points_dev, int64_t n_rows, int
     MODEST_REQUIRE(workspace_bytes >= (int64_t)L.bytes, "workspace smaller than modest_voxelize_workspace_bytes");
     const VxBits bits = vx_bits(cells, batch_cap);
     const char *ws = static_cast<const char *>(workspace_dev);
-    const int fin = bits.passes & 1;
+    const int fin = sort64_result(bits.all);
     const uint64_t *sk = reinterpret_cast<const uint64_t *>(ws + (fin ? L.key_b : L.key_a));
     const uint32_t *si = reinterpret_cast<const uint32_t *>(ws + (fin ? L.idx_b : L.idx_a));
     const int per = VX_FILL_T / 64;

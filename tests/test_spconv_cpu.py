@@ -255,8 +255,9 @@ def test_workspace_does_not_depend_on_the_grid_and_kernels_use_no_scratch():
     assert 0 < sub <= 64 * 160_000 + (1 << 16) and sub < full <= 32 * 27 * 160_000 + (1 << 20)
     assert int(lib.modest_spconv_rulebook_workspace_bytes(0, 27, 0)) >= 0
     res = json.load(open(os.path.join(os.path.dirname(build.LIB), "kernel_resources.json")))
-    mine = {k: v for k, v in res.items() if v.get("file") == "spconv.hip"}
-    assert len(mine) == 21 and sum("sp_gather_gemm" in k for k in mine) == 4 and sum("sp_wgrad_partial" in k for k in mine) == 3
+    mine = {k: v for k, v in res.items() if v.get("file") in ("spconv.hip", "sort64.hip")}
+    assert sum(v["file"] == "spconv.hip" for v in mine.values()) == 18 and sum(v["file"] == "sort64.hip" for v in mine.values()) == 4
+    assert sum("sp_gather_gemm" in k for k in mine) == 4 and sum("sp_wgrad_partial" in k for k in mine) == 3
     assert all(v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 for v in mine.values()), mine
 
 

@@ -219,6 +219,7 @@ def test_kernels_use_no_scratch_memory():
     from modest_amd import build
     build.build(verbose=False)
     res = json.load(open(os.path.join(os.path.dirname(build.LIB), "kernel_resources.json")))
-    mine = {k: v for k, v in res.items() if v.get("file") == "voxelize.hip"}
-    assert len(mine) == 10
+    mine = {k: v for k, v in res.items() if v.get("file") in ("voxelize.hip", "sort64.hip")}
+    assert sum(v["file"] == "voxelize.hip" for v in mine.values()) == 7
+    assert sum(v["file"] == "sort64.hip" for v in mine.values()) == 4   # count, scan, scatter with and without the payload
     assert all(v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0 for v in mine.values()), mine
