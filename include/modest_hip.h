@@ -1008,6 +1008,55 @@ int modest_spconv_wgrad(const float *x_dev, int64_t n_in, int c_in, const float 
                         const int32_t *nbr_dev, int kvol, void *workspace_dev, int64_t workspace_bytes, float *dweight_dev,
                         float *dbias_dev, void *stream);
 
+/* ---- a26 pointnet2_stack_cuda (pcdet/ops/pointnet2/pointnet2_stack/src/, bound at pointnet2_api.cpp) ----
+ * The stacked-batch PointNet++ ops of PV-RCNN and Voxel R-CNN.  All scans of a batch are rows of one (N1 + N2 + ..., C)
+ * tensor; a *_batch_cnt buffer is [dev] int32 (b,), read on the device only: no call copies a count to the host or
+ * synchronises.  Row p belongs to the first scan s with p < cnt[0] + ... + cnt[s], rows past the total to scan b - 1,
+ * negative counts count as 0; the other tensor's rows of that scan are [start_s, start_s + cnt_s), clipped to its real
+ * row count, which every entry point receives.  Every buffer [dev], float32 / int32, contiguous; enqueue only, no context,
+ * 64-bit element offsets.  Furthest point sampling is modest_pn2_furthest_point_sample (the same kernel text).
+ *
+ * ball_query_gpu.cu ball_query_kernel_stack: new_xyz (m,3), xyz (n,3) -> idx (m,nsample): the first nsample rows of the
+ * centre's scan with ((cx-x)^2 + (cy-y)^2) + (cz-z)^2 < radius*radius (float32 product, strict) in index order as
+ * scan-local indices, short rows padded with the first hit; a row without a hit gets idx[0] = -1 and is otherwise left
+ * as given.                                                                                                          */
+int modest_pn2s_ball_query(int b, int m, float radius, int nsample, const float *new_xyz_dev,
+                           const int32_t *new_xyz_batch_cnt_dev, const float *xyz_dev, const int32_t *xyz_batch_cnt_dev,
+                           int n, int32_t *idx_dev, void *stream);
+/* voxel_query_gpu.cu voxel_query_kernel_stack: new_xyz (m,3), xyz (n,3), new_coords (m,4) [batch, z, y, x],
+ * point_indices (b,r1,r2,r3): the row of xyz held by a cell or a negative value.  Cells are visited in dz, dy, dx order
+ * over [-range, +range] per axis; coordinates outside the grid, negative entries, entries >= n and a batch index outside
+ * [0, b) are skipped; a cell is rejected only if d2 > radius*radius.  idx (m,nsample): the first nsample accepted rows of
+ * xyz (global), padded with the first; an empty row gets idx[0] = -1.  At most 2^31 - 1 cells per query inside the grid. */
+int modest_pn2s_voxel_query(int b, int m, int r1, int r2, int r3, int nsample, float radius, int z_range, int y_range,
+                            int x_range, const float *new_xyz_dev, const float *xyz_dev, int n,
+                            const int32_t *new_coords_dev, const int32_t *point_indices_dev, int32_t *idx_dev,
+                            void *stream);
+/* interpolate_gpu.cu three_nn_kernel_stack: unknown (n,3), known (m,3) -> dist2 (n,3) SQUARED distances ascending,
+ * idx (n,3) GLOBAL rows of known (start_s + k); the three smallest (distance, index) pairs within the row's scan; unused
+ * slots hold inf / start_s.                                                                                          */
+int modest_pn2s_three_nn(int b, int n, int m, const float *unknown_dev, const int32_t *unknown_batch_cnt_dev,
+                         const float *known_dev, const int32_t *known_batch_cnt_dev, float *dist2_dev, int32_t *idx_dev,
+                         void *stream);
+/* group_points_gpu.cu group_points_kernel_stack: features (n,c), idx (m,nsample) scan-local -> out (m,c,nsample);
+ * an index outside [0, cnt_s) of the row's scan reads as 0.                                                           */
+int modest_pn2s_group(int b, int m, int c, int nsample, int n, const float *features_dev,
+                      const int32_t *features_batch_cnt_dev, const int32_t *idx_dev, const int32_t *idx_batch_cnt_dev,
+                      float *out_dev, void *stream);
+/* group_points_gpu.cu group_points_grad_kernel_stack: grad_out (m,c,nsample); ADDS into grad_features (n,c) (float
+ * atomics, any order); an index outside its range is skipped, an element no term reaches is not written.             */
+int modest_pn2s_group_grad(int b, int m, int c, int n, int nsample, const float *grad_out_dev, const int32_t *idx_dev,
+                           const int32_t *idx_batch_cnt_dev, const int32_t *features_batch_cnt_dev,
+                           float *grad_features_dev, void *stream);
+/* interpolate_gpu.cu three_interpolate_kernel_stack: features (m,c), idx / weight (n,3) global rows ->
+ * out (n,c) = (w0*f0 + w1*f1) + w2*f2; an index outside [0, m) reads as 0.                                            */
+int modest_pn2s_three_interpolate(int n, int c, int m, const float *features_dev, const int32_t *idx_dev,
+                                  const float *weight_dev, float *out_dev, void *stream);
+/* interpolate_gpu.cu three_interpolate_grad_kernel_stack: grad_out (n,c); ADDS grad_out * weight into
+ * grad_features (m,c) (float atomics, any order); an index outside [0, m) is skipped.                                 */
+int modest_pn2s_three_interpolate_grad(int n, int c, int m, const float *grad_out_dev, const int32_t *idx_dev,
+                                       const float *weight_dev, float *grad_features_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

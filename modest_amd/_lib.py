@@ -105,6 +105,14 @@ SIGNATURES = {
     "modest_pn2_three_nn": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_pn2_three_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_pn2_three_interpolate_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_pn2s_ball_query": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, VP, VP, VP, VP, C.c_int, VP, VP]),
+    "modest_pn2s_voxel_query": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                          C.c_int, VP, VP, C.c_int, VP, VP, VP, VP]),
+    "modest_pn2s_three_nn": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, VP]),
+    "modest_pn2s_group": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "modest_pn2s_group_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP]),
+    "modest_pn2s_three_interpolate": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
+    "modest_pn2s_three_interpolate_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "modest_roipoint_pool3d": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP]),
     "modest_points_in_boxes": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
     "modest_voxelize_host": (C.c_int64, [VP, C.c_int64, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP, VP, VP]),

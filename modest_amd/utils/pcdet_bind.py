@@ -12,6 +12,10 @@ the shims open the library at their first call.
 
 ``install(sparse_conv=True)`` binds ``modest_amd.utils.spconv`` -- the sparse 3-D convolutions SECOND's backbone is built
 from -- as ``spconv`` instead of the stand-in; ``spconv.utils`` is the same module either way.
+
+``install(point_stack=True)`` binds ``modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda`` -- the
+stacked-batch PointNet++ ops of PV-RCNN and Voxel R-CNN -- under the reference's name instead of
+the stand-in.
 """
 import importlib
 import importlib.util
@@ -30,6 +34,8 @@ SHIMS = {
 STAND_INS = ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda", "spconv")
 SPCONV_UTILS = "modest_amd.utils.spconv_utils"   # bound as spconv.utils while spconv itself is a stand-in
 SPCONV = "modest_amd.utils.spconv"               # bound as spconv by install(sparse_conv=True)
+POINT_STACK_NAME = STAND_INS[0]                  # bound to POINT_STACK by install(point_stack=True)
+POINT_STACK = "modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda"
 
 
 class StandIn(types.ModuleType):
@@ -61,11 +67,25 @@ def _bind_sparse_conv():
     return ours
 
 
-def install(stand_ins=True, sparse_conv=False):
+def _bind_point_stack():
+    """the stack extension's name := our shim unless something else is bound there -> the module bound, or None"""
+    ours = importlib.import_module(POINT_STACK)
+    mod = sys.modules.get(POINT_STACK_NAME)
+    if mod is not None and mod is not ours and not isinstance(mod, StandIn):
+        return None   # neither ours nor a stand-in (the compiled extension): leave it alone
+    sys.modules[POINT_STACK_NAME] = ours
+    return ours
+
+
+def install(stand_ins=True, sparse_conv=False, point_stack=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     for name, target in SHIMS.items():
         bound[name] = sys.modules[name] = importlib.import_module(target)
+    if point_stack:
+        ours = _bind_point_stack()
+        if ours is not None and not stand_ins:
+            bound[POINT_STACK_NAME] = ours
     if sparse_conv:
         ours = _bind_sparse_conv()
         if ours is not None and not stand_ins:
