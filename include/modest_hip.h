@@ -1057,6 +1057,28 @@ int modest_pn2s_three_interpolate(int n, int c, int m, const float *features_dev
 int modest_pn2s_three_interpolate_grad(int n, int c, int m, const float *grad_out_dev, const int32_t *idx_dev,
                                        const float *weight_dev, float *grad_features_dev, void *stream);
 
+/* ---- a27 anchor target assignment (AxisAlignedTargetAssigner.assign_targets of OpenPCDet's anchor heads) ----
+ * POS_FRACTION < 0, MATCH_HEIGHT and NORM_BY_NUM_EXAMPLES off.  A whole batch, all anchor classes, in one call: enqueue
+ * only, no context, no device allocation, no synchronise, nothing read back; the (anchors, gts) IoU matrix is never stored.
+ * Every buffer [dev].
+ *   gt       (b, m, gt_cols) float32 with the three strides given in elements: 7 + Cg box values and the class id;
+ *   anchors  (sum of rows, a_cols = 7 + Ca) float32, contiguous, the classes' blocks one after the other;
+ *   cls      (n_cls, 5) int64: first row, rows, k, stride, offset -- row i of the class goes to output row
+ *            (i / k) * stride + offset + i % k of its sample (k >= 1; the map over all classes is one to one onto [0, n_out));
+ *   thr      (n_cls, 2) float32 matched, unmatched;
+ *   match    (n_cls, n_names) uint8: 1 where class_names[n] is the anchor class's name.  Class id c names entry c - 1,
+ *            id <= 0 wraps once as Python does; an id outside belongs to no class;
+ *   max_cls_rows  the largest number of rows of a class (sizes the grid).
+ * Outputs, every element written: labels int32 (b, n_out), targets float32 (b, n_out, 7 + sincos + min(Ca, Cg)),
+ * weights float32 (b, n_out).  workspace 4-byte aligned, modest_anchor_targets_workspace_bytes(b, n_cls, m) bytes, need
+ * not be initialised.  The column maxima are merged with integer atomicMax on float bits: no result depends on order. */
+int64_t modest_anchor_targets_workspace_bytes(int b, int n_cls, int m);
+int modest_anchor_targets(int b, int m, int gt_cols, const float *gt_dev, int64_t gt_stride_b, int64_t gt_stride_m,
+                          int64_t gt_stride_c, const float *anchors_dev, int a_cols, int n_cls, const int64_t *cls_dev,
+                          const float *thr_dev, const uint8_t *match_dev, int n_names, int64_t max_cls_rows, int sincos,
+                          int64_t n_out, int32_t *labels_dev, float *targets_dev, float *weights_dev, void *workspace_dev,
+                          int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,9 @@ SIGNATURES = {
     "modest_spconv_wgrad_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "modest_spconv_wgrad": (C.c_int, [VP, C.c_int64, C.c_int, VP, C.c_int64, C.c_int, VP, C.c_int, VP, C.c_int64, VP, VP,
                                       VP]),
+    "modest_anchor_targets_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "modest_anchor_targets": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, VP, C.c_int, C.c_int,
+                                        VP, VP, VP, C.c_int, C.c_int64, C.c_int, C.c_int64, VP, VP, VP, VP, C.c_int64, VP]),
 }
 
 _lib = None

@@ -1315,3 +1315,53 @@ def spconv_backward(features: torch.Tensor, weight: torch.Tensor, grad_out: torc
             if not need_weight_grad:
                 dw = None
     return dx, dw, db
+
+
+# --------------------------------------------------------------------------- anchor target assignment
+def anchor_targets_workspace_bytes(batch_size: int, n_cls: int, m: int) -> int:
+    nb = int(load().modest_anchor_targets_workspace_bytes(int(batch_size), int(n_cls), int(m)))
+    if nb < 0:
+        check(nb, "modest_anchor_targets_workspace_bytes")
+    return nb
+
+
+def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Tensor, thresholds: torch.Tensor,
+                   name_match: torch.Tensor, max_cls_rows: int, n_out: int, sincos: bool = False,
+                   workspace: Optional[torch.Tensor] = None):
+    """modest_anchor_targets on PyTorch's current stream: enqueue only, nothing is read back.
+    gt (B, M, 7 + Cg + 1) float32, any strides; anchors (sum of rows, 7 + Ca) float32, the classes' blocks one after the
+    other; cls_table (n_cls, 5) int64 [first row, rows, k, stride, offset] (row i of a class -> output row
+    (i / k) * stride + offset + i % k); thresholds (n_cls, 2) float32 [matched, unmatched]; name_match (n_cls, n_names)
+    uint8.  -> labels (B, n_out) int32, targets (B, n_out, 7 + sincos + min(Ca, Cg)) float32, weights (B, n_out) float32."""
+    lib = load()
+    if not gt.is_cuda or gt.dtype != torch.float32 or gt.ndim != 3:
+        raise ValueError("gt must be a (B, M, 8 + C) float32 device tensor")
+    _dev(anchors, torch.float32, "anchors")
+    _dev(cls_table, torch.int64, "cls_table")
+    _dev(thresholds, torch.float32, "thresholds")
+    _dev(name_match, torch.uint8, "name_match")
+    B, M, G = (int(v) for v in gt.shape)
+    n_cls = int(cls_table.shape[0])
+    if anchors.ndim != 2 or anchors.shape[1] < 7 or G < 8:
+        raise ValueError(f"anchors has shape {tuple(anchors.shape)} and gt {tuple(gt.shape)}: expected (N, 7 + Ca) and (B, M, 7 + Cg + 1)")
+    A = int(anchors.shape[1])
+    if tuple(cls_table.shape) != (n_cls, 5) or tuple(thresholds.shape) != (n_cls, 2) or name_match.ndim != 2 \
+            or name_match.shape[0] != n_cls:
+        raise ValueError("cls_table (n_cls, 5), thresholds (n_cls, 2) and name_match (n_cls, n_names) disagree")
+    dev = gt.device
+    code = 7 + int(bool(sincos)) + min(A - 7, G - 8)
+    labels = torch.empty((B, n_out), dtype=torch.int32, device=dev)
+    targets = torch.empty((B, n_out, code), dtype=torch.float32, device=dev)
+    weights = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+    nbytes = anchor_targets_workspace_bytes(B, n_cls, M)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    sb, sm, sc = (int(v) for v in gt.stride())
+    with torch.cuda.device(dev):
+        check(lib.modest_anchor_targets(B, M, G, gt.data_ptr(), sb, sm, sc, anchors.data_ptr(), A, n_cls,
+                                        cls_table.data_ptr(), thresholds.data_ptr(), name_match.data_ptr(),
+                                        int(name_match.shape[1]), int(max_cls_rows), int(bool(sincos)), int(n_out),
+                                        labels.data_ptr(), targets.data_ptr(), weights.data_ptr(), workspace.data_ptr(),
+                                        workspace.numel(), _stream()), "modest_anchor_targets")
+    return labels, targets, weights

@@ -16,6 +16,11 @@ from -- as ``spconv`` instead of the stand-in; ``spconv.u
 ``install(point_stack=True)`` binds ``modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda`` -- the
 stacked-batch PointNet++ ops of PV-RCNN and Voxel R-CNN -- under the reference's name instead of
 the stand-in.
+
+``install(anchor_targets=True)`` binds ``modest_amd.utils.target_assigner`` -- the anchor target assignment of the anchor
+heads on the GPU -- as ``pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner``.
+Call it before ``pcdet.models`` is imported: ``anchor_head_template`` takes the class from that module when it is first
+imported.  A module already imported under that name is left alone.
 """
 import importlib
 import importlib.util
@@ -36,6 +41,8 @@ SPCONV_UTILS = "modest_amd.utils.spconv_utils"   # bound as spconv.utils while s
 SPCONV = "modest_amd.utils.spconv"               # bound as spconv by install(sparse_conv=True)
 POINT_STACK_NAME = STAND_INS[0]                  # bound to POINT_STACK by install(point_stack=True)
 POINT_STACK = "modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda"
+ANCHOR_TARGETS_NAME = "pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner"
+ANCHOR_TARGETS = "modest_amd.utils.target_assigner"   # bound to ANCHOR_TARGETS_NAME by install(anchor_targets=True)
 
 
 class StandIn(types.ModuleType):
@@ -77,11 +84,25 @@ def _bind_point_stack():
     return ours
 
 
-def install(stand_ins=True, sparse_conv=False, point_stack=False):
+def _bind_anchor_targets():
+    """the reference assigner's module name := our module unless the reference's is already imported -> the module bound, or None"""
+    ours = importlib.import_module(ANCHOR_TARGETS)
+    mod = sys.modules.get(ANCHOR_TARGETS_NAME)
+    if mod is not None and mod is not ours:
+        return None   # already imported (anchor_head_template holds its class): leave it alone
+    sys.modules[ANCHOR_TARGETS_NAME] = ours
+    return ours
+
+
+def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     for name, target in SHIMS.items():
         bound[name] = sys.modules[name] = importlib.import_module(target)
+    if anchor_targets:
+        ours = _bind_anchor_targets()
+        if ours is not None:
+            bound[ANCHOR_TARGETS_NAME] = ours
     if point_stack:
         ours = _bind_point_stack()
         if ours is not None and not stand_ins:
