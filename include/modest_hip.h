@@ -1079,6 +1079,43 @@ int modest_anchor_targets(int b, int m, int gt_cols, const float *gt_dev, int64_
                           int64_t n_out, int32_t *labels_dev, float *targets_dev, float *weights_dev, void *workspace_dev,
                           int64_t workspace_bytes, void *stream);
 
+/* ---- a28 roiaware_pool3d_cuda.forward / backward: the RoI-aware voxel pooling of PartA2 ---------
+ * Every buffer [dev], float32 / int32, contiguous; enqueue only, no context, no device allocation, no synchronise.
+ * Element offsets are 64-bit.  rois (boxes_num,7) [cx,cy,cz,dx,dy,dz,rz], pts (pts_num,3), pts_feature (pts_num,channels),
+ * argmax and pooled_features (boxes_num,out_x,out_y,out_z,channels), pts_idx_of_voxels (boxes_num,out_x,out_y,out_z,
+ * max_pts_each_voxel).  pool_method 0 = max, 1 = avg, anything else is an error.  out_x, out_y, out_z in 1..256 (the
+ * reference packs each index into 8 bits) and out_x * out_y * out_z <= 13824 in the forward (one LDS counter per voxel):
+ * a larger grid fails the call and launches nothing.  max_pts_each_voxel >= 1 (1: every list stays empty).
+ *
+ * roiaware_pool3d_kernel.cu:39-233 roiaware_pool3d_launcher.  A point inside a box by the predicate of a23 falls into the
+ * voxel index = min(max((unsigned)(int)q, 0), out - 1), q = (l + d / 2.0f) / (d / (float)out) in float32 with correctly
+ * rounded divisions, per axis (lx, ly of the predicate, lz = z - cz): NaN -> 0, q <= -1 -> out - 1, q >= out -> out - 1,
+ * otherwise truncation toward zero.  Word 0 of a voxel's list is its count, capped at max_pts_each_voxel - 1, and is
+ * WRITTEN whatever it held (the reference increments the given word: its caller zero-fills); words 1..count are the
+ * voxel's points in ascending index, later ones are dropped; words beyond count are left as given.  No (boxes, points)
+ * intermediate.  max: the list is walked in slot order, a value wins if it is > the best so far, from -inf (first of
+ * equal maxima; -inf and NaN never win); argmax is written for every element (-1 for none), pooled_features only where
+ * argmax != -1.  avg: the float32 sum in slot order from +0 divided by (float)count, written only where count > 0; argmax
+ * is not touched.  channels == 0, boxes_num == 0 and pts_num == 0 are legal (no points: every count is written as 0).
+ *
+ * roiaware_pool3d_kernel.cu:236-310 roiaware_pool3d_backward_launcher.  ADDS into grad_in (pts_num,channels) (the caller
+ * zero-fills, as the reference's Python side does): avg grad_out[b][v][c] * (1.0f / fmaxf((float)count, 1.0f)) to every
+ * point of the voxel's list, max grad_out[b][v][c] to point argmax[b][v][c].  The sum for one (point, channel) runs over
+ * the boxes in ascending index without float atomics, so its bits do not change from run to run (the reference's
+ * atomicAdd order does).  pts_idx_of_voxels and argmax must come from one forward call; an argmax entry that names a
+ * point outside that voxel's list contributes nothing, list entries outside [0, pts_num) are ignored.  workspace:
+ * modest_roiaware_pool3d_backward_workspace_bytes(boxes_num, pts_num) bytes (a (pts_num, boxes_num) int32 table), 4-byte
+ * aligned, need not be initialised.  Any size 0 writes nothing.                                                       */
+int modest_roiaware_pool3d_forward(int boxes_num, int pts_num, int channels, int max_pts_each_voxel, int out_x, int out_y,
+                                   int out_z, const float *rois_dev, const float *pts_dev, const float *pts_feature_dev,
+                                   int32_t *argmax_dev, int32_t *pts_idx_of_voxels_dev, float *pooled_features_dev,
+                                   int pool_method, void *stream);
+int64_t modest_roiaware_pool3d_backward_workspace_bytes(int boxes_num, int pts_num);
+int modest_roiaware_pool3d_backward(int boxes_num, int pts_num, int out_x, int out_y, int out_z, int channels,
+                                    int max_pts_each_voxel, const int32_t *pts_idx_of_voxels_dev, const int32_t *argmax_dev,
+                                    const float *grad_out_dev, float *grad_in_dev, int pool_method, void *workspace_dev,
+                                    int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ SIGNATURES = {
     "modest_anchor_targets_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "modest_anchor_targets": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, VP, C.c_int, C.c_int,
                                         VP, VP, VP, C.c_int, C.c_int64, C.c_int, C.c_int64, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_roiaware_pool3d_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP,
+                                                 VP, VP, C.c_int, VP]),
+    "modest_roiaware_pool3d_backward_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "modest_roiaware_pool3d_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP,
+                                                  C.c_int, VP, C.c_int64, VP]),
 }
 
 _lib = None

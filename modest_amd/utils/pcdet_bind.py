@@ -21,6 +21,10 @@ the stand-in.
 heads on the GPU -- as ``pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner``.
 Call it before ``pcdet.models`` is imported: ``anchor_head_template`` takes the class from that module when it is first
 imported.  A module already imported under that name is left alone.
+
+``install(roiaware_pool=True)`` binds ``modest_amd.utils.roiaware_voxel_pool_cuda`` -- the full ``roiaware_pool3d_cuda``
+with PartA2's RoI-aware voxel pooling ``forward`` / ``backward`` -- under the reference's name
+instead of the module whose ``forward`` / ``backward`` are not provided.  A module that is neither of ours is left alone.
 """
 import importlib
 import importlib.util
@@ -43,6 +47,8 @@ POINT_STACK_NAME = STAND_INS[0]                  # bound to POINT_STACK by insta
 POINT_STACK = "modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda"
 ANCHOR_TARGETS_NAME = "pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner"
 ANCHOR_TARGETS = "modest_amd.utils.target_assigner"   # bound to ANCHOR_TARGETS_NAME by install(anchor_targets=True)
+ROIAWARE_NAME = "pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"
+ROIAWARE_POOL = "modest_amd.utils.roiaware_voxel_pool_cuda"   # bound to ROIAWARE_NAME by install(roiaware_pool=True)
 
 
 class StandIn(types.ModuleType):
@@ -94,11 +100,25 @@ def _bind_anchor_targets():
     return ours
 
 
-def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False):
+def _bind_roiaware_pool(before):
+    """the roiaware extension's name := the full drop-in unless `before`, what was bound there when install() was
+    called, is neither absent nor ours -> the module bound, or None"""
+    ours = importlib.import_module(ROIAWARE_POOL)
+    if before is not None and before is not ours and before is not importlib.import_module(SHIMS[ROIAWARE_NAME]):
+        sys.modules[ROIAWARE_NAME] = before   # a foreign module (the compiled extension): put it back
+        return None
+    sys.modules[ROIAWARE_NAME] = ours
+    return ours
+
+
+def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
+    roiaware_before = sys.modules.get(ROIAWARE_NAME)
     for name, target in SHIMS.items():
         bound[name] = sys.modules[name] = importlib.import_module(target)
+    if roiaware_pool:
+        bound[ROIAWARE_NAME] = _bind_roiaware_pool(roiaware_before) or roiaware_before
     if anchor_targets:
         ours = _bind_anchor_targets()
         if ours is not None:

@@ -9,8 +9,9 @@ code use it:
 * ``points_in_boxes_cpu(boxes, pts, pts_indices) -> 1`` -- pure host code (numpy,
   ``kitti_infos.points_in_boxes_host``: the reference's host predicate with the host C library's
   ``cosf`` / ``sinf``).  OpenPCDet calls it from DataLoader workers; it never opens the GPU.
-* ``forward`` / ``backward`` -- the RoI-aware voxel pooling of PartA2 is not provided: they raise
-  ``NotImplementedError``.
+* ``forward`` / ``backward`` -- the RoI-aware voxel pooling of PartA2 is not provided BY THIS MODULE: they raise
+  ``NotImplementedError``.  The full drop-in, with both, is ``modest_amd.utils.roiaware_voxel_pool_cuda``
+  (``pcdet_bind.install(roiaware_pool=True)``).
 
 Bound as ``sys.modules["pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"]`` (INTEGRATION.md,
 ``modest_amd.utils.pcdet_bind.install``).
