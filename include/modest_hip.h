@@ -1116,6 +1116,31 @@ int modest_roiaware_pool3d_backward(int boxes_num, int pts_num, int out_x, int o
                                     const float *grad_out_dev, float *grad_in_dev, int pool_method, void *workspace_dev,
                                     int64_t workspace_bytes, void *stream);
 
+/* ---- a29 inverse sparse 3-D convolution (spconv 1.2's SparseInverseConv3d) ----------------------
+ * An inverse convolution runs a strided convolution's rulebook backwards: its output rows are that convolution's input
+ * sites, out[i] = sum over k ascending with nbr_t[k][i] >= 0, ci ascending, of x[nbr_t[k][i]][ci] * weight[k][ci][co].
+ * That is modest_spconv_gather_gemm on nbr_t; the two entry points below do the same sum on tiles of one class.
+ * The class of row i = [b, z, y, x] is ((z + p_z) % s_z * s_y + (y + p_y) % s_y) * s_x + (x + p_x) % s_x, one of
+ * s_z s_y s_x classes (strides 1 .. 64): the row can only be read at offsets with k_j == residue_j (mod s_j).
+ * class_order: perm [dev] (n_rows,) int32 = the rows stably ordered by class (numpy's argsort(class, kind="stable")),
+ * class_start [dev] (classes + 1,) int32 = the exclusive counts, class_start[classes] = n_rows.  workspace [dev],
+ * 256-byte aligned, modest_spconv_class_order_workspace_bytes bytes, a function of n_rows alone.  Enqueue only: no
+ * synchronise, no count travels to the host, nothing depends on the order in which atomics land.                        */
+int64_t modest_spconv_class_order_workspace_bytes(int64_t n_rows, int n_classes);
+int modest_spconv_class_order(const int32_t *indices_dev, int64_t n_rows, const int32_t *stride3_host,
+                              const int32_t *pad3_host, void *workspace_dev, int64_t workspace_bytes, int32_t *perm_dev,
+                              int32_t *class_start_dev, void *stream);
+/* in (n_in, in_channels), weight (kernel volume, in_channels, w_cout), map = nbr_t (kernel volume, n_out), perm and
+ * class_start as class_order wrote them for the same rows and strides, at most 64 classes -> out (n_out, w_cout), every
+ * element written exactly once (a row that nothing reads gets +0.0, or the bias).  A workgroup owns 64 consecutive
+ * entries of perm inside one class and visits only that class's offsets, ascending; the grid is n_out / 64 + classes,
+ * the surplus workgroups exit at once.  Bit for bit what modest_spconv_gather_gemm(transposed = 0) writes for the same
+ * map.  Channels 1 .. 128, kernel sizes 1 .. 7.  Enqueue only.                                                          */
+int modest_spconv_gather_gemm_classes(const float *in_dev, int64_t n_in, int in_channels, const float *weight_dev,
+                                      const int32_t *kernel3_host, const int32_t *stride3_host, int w_cout,
+                                      const float *bias_dev, const int32_t *map_dev, int64_t n_out, const int32_t *perm_dev,
+                                      const int32_t *class_start_dev, float *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,10 @@ SIGNATURES = {
     "modest_roiaware_pool3d_backward_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "modest_roiaware_pool3d_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP,
                                                   C.c_int, VP, C.c_int64, VP]),
+    "modest_spconv_class_order_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "modest_spconv_class_order": (C.c_int, [VP, C.c_int64, VP, VP, VP, C.c_int64, VP, VP, VP]),
+    "modest_spconv_gather_gemm_classes": (C.c_int, [VP, C.c_int64, C.c_int, VP, VP, VP, C.c_int, VP, VP, C.c_int64, VP, VP,
+                                                    VP, VP]),
 }
 
 _lib = None

@@ -1317,6 +1317,142 @@ def spconv_backward(features: torch.Tensor, weight: torch.Tensor, grad_out: torc
     return dx, dw, db
 
 
+# --------------------------------------------------------------------------- inverse sparse convolution
+SPCONV_INVERSE_CALLS = {"class_order": 0, "forward": 0, "input_grad": 0, "weight_grad": 0}   # library calls made, by kind
+SPCONV_INVERSE_ORDER = "classes"   # the default `order` of spconv_inverse_forward ("Measurement")
+SPCONV_CLASSES_MAX = 64            # the class tiles apply for 2 .. 64 classes, the rows of nbr_t otherwise
+
+
+def spconv_classes(rb: SpconvRulebook) -> int:
+    """s_z s_y s_x of a strided rulebook: the classes its input rows fall into"""
+    return rb.stride[0] * rb.stride[1] * rb.stride[2]
+
+
+def _spconv_inverse_rulebook(rb: SpconvRulebook):
+    if not isinstance(rb, SpconvRulebook):
+        raise ValueError("an inverse convolution needs the rulebook of a strided convolution")
+    if rb.subm:
+        raise ValueError("an inverse convolution needs the rulebook of a strided convolution, this one is submanifold")
+
+
+def spconv_class_order(rb: SpconvRulebook):
+    """-> (perm (N_in,) int32, class_start (C + 1,) int32) on the device: the input rows of a strided rulebook stably
+    ordered by the class ((z + p_z) % s_z, (y + p_y) % s_y, (x + p_x) % s_x), and the exclusive counts.  Built at the
+    first call and kept on the rulebook.  Enqueue only."""
+    _spconv_inverse_rulebook(rb)
+    cached = getattr(rb, "class_order", None)
+    if cached is not None:
+        return cached
+    _dev(rb.indices, torch.int32, "indices")
+    dev = rb.indices.device
+    lib = load()
+    classes = spconv_classes(rb)
+    nbytes = int(lib.modest_spconv_class_order_workspace_bytes(rb.n_in, classes))
+    if nbytes < 0:
+        check(nbytes, "modest_spconv_class_order_workspace_bytes")
+    stride, pad = (np.ascontiguousarray(v, dtype=np.int32) for v in (rb.stride, rb.padding))
+    with torch.cuda.device(dev):
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        perm = torch.empty((rb.n_in,), dtype=torch.int32, device=dev)
+        class_start = torch.empty((classes + 1,), dtype=torch.int32, device=dev)
+        SPCONV_INVERSE_CALLS["class_order"] += 1
+        check(lib.modest_spconv_class_order(rb.indices.data_ptr(), rb.n_in, _np_ptr(stride), _np_ptr(pad), ws.data_ptr(),
+                                            ws.numel(), perm.data_ptr(), class_start.data_ptr(), _stream()),
+              "modest_spconv_class_order")
+    rb.class_order = (perm, class_start)
+    return rb.class_order
+
+
+def _spconv_inverse_args(features, weight, rb):
+    _spconv_inverse_rulebook(rb)
+    cin, cout = _spconv_weight(weight, rb)
+    _dev(features, torch.float32, "features")
+    if tuple(features.shape) != (rb.n_out, cin):
+        raise ValueError(f"features has shape {tuple(features.shape)}, expected {(rb.n_out, cin)}: the rows of the strided "
+                         f"convolution's output")
+    return cin, cout
+
+
+def spconv_inverse_forward(features: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rb: SpconvRulebook,
+                           out: Optional[torch.Tensor] = None, order: Optional[str] = None) -> torch.Tensor:
+    """The strided rulebook rb run backwards: features (rb.n_out, Cin) on the coarse sites, weight (kz, ky, kx, Cin, Cout)
+    or (K, Cin, Cout), bias (Cout,) or None -> (rb.n_in, Cout) on the fine sites, every element written, in the fixed
+    order of DESIGN.md section 7k.  order "classes": tiles of one class (2 .. 64 classes; otherwise the rows are used);
+    "rows": modest_spconv_gather_gemm on nbr_t.  The same bits either way.  Enqueue only."""
+    order = SPCONV_INVERSE_ORDER if order is None else order
+    if order not in ("classes", "rows"):
+        raise ValueError(f"order must be 'classes' or 'rows', got {order!r}")
+    cin, cout = _spconv_inverse_args(features, weight, rb)
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (cout,):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected {(cout,)}")
+    if out is None:
+        out = torch.empty((rb.n_in, cout), dtype=torch.float32, device=features.device)
+    _dev(out, torch.float32, "out")
+    if tuple(out.shape) != (rb.n_in, cout):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(rb.n_in, cout)}")
+    lib = load()
+    bias_ptr = bias.data_ptr() if bias is not None else None
+    if order == "classes" and 2 <= spconv_classes(rb) <= SPCONV_CLASSES_MAX:
+        perm, class_start = spconv_class_order(rb)
+        kernel, stride = (np.ascontiguousarray(v, dtype=np.int32) for v in (rb.kernel, rb.stride))
+        SPCONV_INVERSE_CALLS["forward"] += 1
+        with torch.cuda.device(features.device):
+            check(lib.modest_spconv_gather_gemm_classes(features.data_ptr(), rb.n_out, cin, weight.data_ptr(), _np_ptr(kernel),
+                                                        _np_ptr(stride), cout, bias_ptr, rb.nbr_t.data_ptr(), rb.n_in,
+                                                        perm.data_ptr(), class_start.data_ptr(), out.data_ptr(), _stream()),
+                  "modest_spconv_gather_gemm_classes")
+        return out
+    SPCONV_INVERSE_CALLS["forward"] += 1
+    with torch.cuda.device(features.device):
+        check(lib.modest_spconv_gather_gemm(features.data_ptr(), rb.n_out, cin, weight.data_ptr(), rb.kvol, cin, cout, 0,
+                                            bias_ptr, rb.nbr_t.data_ptr(), rb.n_in, out.data_ptr(), _stream()),
+              "modest_spconv_gather_gemm")
+    return out
+
+
+def spconv_inverse_backward(features: torch.Tensor, weight: torch.Tensor, grad_out: torch.Tensor, rb: SpconvRulebook,
+                            need_input_grad: bool = True, need_weight_grad: bool = True, need_bias_grad: bool = True,
+                            grad_input: Optional[torch.Tensor] = None):
+    """-> (grad_input (rb.n_out, Cin) | None, grad_weight (shape of weight) | None, grad_bias (Cout,) | None) for grad_out
+    (rb.n_in, Cout).  The feature gradient is the gather-GEMM with the transposed weights on nbr, the weight gradient
+    modest_spconv_wgrad over the coarse rows with the two sides exchanged, (K, Cout, Cin), transposed once; the bias
+    gradient is the column sum of grad_out.  A gradient that is not needed launches nothing.  Enqueue only."""
+    cin, cout = _spconv_inverse_args(features, weight, rb)
+    _dev(grad_out, torch.float32, "grad_out")
+    if tuple(grad_out.shape) != (rb.n_in, cout):
+        raise ValueError(f"grad_out has shape {tuple(grad_out.shape)}, expected {(rb.n_in, cout)}")
+    dev = features.device
+    lib = load()
+    dx = dw = db = None
+    with torch.cuda.device(dev):
+        if need_input_grad:
+            if grad_input is None:
+                grad_input = torch.empty((rb.n_out, cin), dtype=torch.float32, device=dev)
+            dx = _dev(grad_input, torch.float32, "grad_input")
+            if tuple(dx.shape) != (rb.n_out, cin):
+                raise ValueError(f"grad_input has shape {tuple(dx.shape)}, expected {(rb.n_out, cin)}")
+            SPCONV_INVERSE_CALLS["input_grad"] += 1
+            check(lib.modest_spconv_gather_gemm(grad_out.data_ptr(), rb.n_in, cout, weight.data_ptr(), rb.kvol, cin, cout, 1,
+                                                None, rb.nbr.data_ptr(), rb.n_out, dx.data_ptr(), _stream()),
+                  "modest_spconv_gather_gemm")
+        if need_weight_grad:
+            nbytes = int(lib.modest_spconv_wgrad_workspace_bytes(rb.n_out, rb.kvol, cout, cin))
+            if nbytes < 0:
+                check(nbytes, "modest_spconv_wgrad_workspace_bytes")
+            ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+            dwt = torch.empty((rb.kvol, cout, cin), dtype=torch.float32, device=dev)
+            SPCONV_INVERSE_CALLS["weight_grad"] += 1
+            check(lib.modest_spconv_wgrad(grad_out.data_ptr(), rb.n_in, cout, features.data_ptr(), rb.n_out, cin,
+                                          rb.nbr.data_ptr(), rb.kvol, ws.data_ptr(), ws.numel(), dwt.data_ptr(), None,
+                                          _stream()), "modest_spconv_wgrad")
+            dw = dwt.transpose(1, 2).contiguous().view(weight.shape)
+        if need_bias_grad:
+            db = grad_out.sum(0)
+    return dx, dw, db
+
+
 # --------------------------------------------------------------------------- anchor target assignment (DESIGN.md section 7i)
 def anchor_targets_workspace_bytes(batch_size: int, n_cls: int, m: int) -> int:
     nb = int(load().modest_anchor_targets_workspace_bytes(int(batch_size), int(n_cls), int(m)))

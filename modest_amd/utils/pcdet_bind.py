@@ -25,6 +25,10 @@ imported.  A module already imported under that name is left alone.
 ``install(roiaware_pool=True)`` binds ``modest_amd.utils.roiaware_voxel_pool_cuda`` -- the full ``roiaware_pool3d_cuda``
 with PartA2's RoI-aware voxel pooling ``forward`` / ``backward`` -- under the reference's name
 instead of the module whose ``forward`` / ``backward`` are not provided.  A module that is neither of ours is left alone.
+
+``install(sparse_inverse=True)`` binds ``modest_amd.utils.spconv_inverse`` -- ``modest_amd.utils.spconv`` plus
+``SparseInverseConv3d``, what PartA2's ``UNetV2`` is built from -- as ``spconv``, in place of the
+stand-in or of ``modest_amd.utils.spconv``; an installed or imported spconv is left alone.
 """
 import importlib
 import importlib.util
@@ -43,6 +47,7 @@ SHIMS = {
 STAND_INS = ("pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda", "spconv")
 SPCONV_UTILS = "modest_amd.utils.spconv_utils"   # bound as spconv.utils while spconv itself is a stand-in
 SPCONV = "modest_amd.utils.spconv"               # bound as spconv by install(sparse_conv=True)
+SPCONV_INVERSE = "modest_amd.utils.spconv_inverse"   # bound as spconv by install(sparse_inverse=True)
 POINT_STACK_NAME = STAND_INS[0]                  # bound to POINT_STACK by install(point_stack=True)
 POINT_STACK = "modest_amd.utils.pointnet2.pointnet2_stack.pointnet2_stack_cuda"
 ANCHOR_TARGETS_NAME = "pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner"
@@ -80,6 +85,19 @@ def _bind_sparse_conv():
     return ours
 
 
+def _bind_sparse_inverse():
+    """spconv := modest_amd.utils.spconv_inverse unless a real spconv is imported or installed -> the module bound, or None"""
+    ours = importlib.import_module(SPCONV_INVERSE)
+    mod = sys.modules.get("spconv")
+    if mod is None and importlib.util.find_spec("spconv") is not None:
+        return None   # the real package is installed: leave it alone
+    if mod is not None and mod is not ours and mod is not importlib.import_module(SPCONV) and not isinstance(mod, StandIn):
+        return None   # ... or already imported
+    sys.modules["spconv"] = ours
+    sys.modules["spconv.utils"] = ours.utils
+    return ours
+
+
 def _bind_point_stack():
     """the stack extension's name := our shim unless something else is bound there -> the module bound, or None"""
     ours = importlib.import_module(POINT_STACK)
@@ -111,7 +129,8 @@ def _bind_roiaware_pool(before):
     return ours
 
 
-def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False):
+def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
+            sparse_inverse=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     roiaware_before = sys.modules.get(ROIAWARE_NAME)
@@ -129,6 +148,10 @@ def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets
             bound[POINT_STACK_NAME] = ours
     if sparse_conv:
         ours = _bind_sparse_conv()
+        if ours is not None and not stand_ins:
+            bound["spconv"] = ours
+    if sparse_inverse:
+        ours = _bind_sparse_inverse()
         if ours is not None and not stand_ins:
             bound["spconv"] = ours
     if stand_ins:
