@@ -1463,12 +1463,14 @@ def anchor_targets_workspace_bytes(batch_size: int, n_cls: int, m: int) -> int:
 
 def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Tensor, thresholds: torch.Tensor,
                    name_match: torch.Tensor, max_cls_rows: int, n_out: int, sincos: bool = False,
-                   workspace: Optional[torch.Tensor] = None):
+                   workspace: Optional[torch.Tensor] = None, out=None):
     """modest_anchor_targets on PyTorch's current stream: enqueue only, nothing is read back.
     gt (B, M, 7 + Cg + 1) float32, any strides; anchors (sum of rows, 7 + Ca) float32, the classes' blocks one after the
     other; cls_table (n_cls, 5) int64 [first row, rows, k, stride, offset] (row i of a class -> output row
     (i / k) * stride + offset + i % k); thresholds (n_cls, 2) float32 [matched, unmatched]; name_match (n_cls, n_names)
-    uint8.  -> labels (B, n_out) int32, targets (B, n_out, 7 + sincos + min(Ca, Cg)) float32, weights (B, n_out) float32."""
+    uint8.  -> labels (B, n_out) int32, targets (B, n_out, 7 + sincos + min(Ca, Cg)) float32, weights (B, n_out) float32:
+    freshly allocated, or the three tensors of `out` (of exactly these shapes and types, contiguous, on gt's device), every
+    element of which is written."""
     lib = load()
     if not gt.is_cuda or gt.dtype != torch.float32 or gt.ndim != 3:
         raise ValueError("gt must be a (B, M, 8 + C) float32 device tensor")
@@ -1486,9 +1488,19 @@ def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Ten
         raise ValueError("cls_table (n_cls, 5), thresholds (n_cls, 2) and name_match (n_cls, n_names) disagree")
     dev = gt.device
     code = 7 + int(bool(sincos)) + min(A - 7, G - 8)
-    labels = torch.empty((B, n_out), dtype=torch.int32, device=dev)
-    targets = torch.empty((B, n_out, code), dtype=torch.float32, device=dev)
-    weights = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+    want = (("labels", torch.int32, (B, int(n_out))), ("targets", torch.float32, (B, int(n_out), code)),
+            ("weights", torch.float32, (B, int(n_out))))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
+    if len(out) != 3:
+        raise ValueError("out must be (labels, targets, weights)")
+    for t, (name, dtype, shape) in zip(out, want):
+        _dev(t, dtype, f"out {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.device != dev:
+            raise ValueError(f"out {name} is on {t.device}, gt on {dev}")
+    labels, targets, weights = out
     nbytes = anchor_targets_workspace_bytes(B, n_cls, M)
     if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
         workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)

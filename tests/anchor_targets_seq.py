@@ -216,6 +216,10 @@ def assign(cfg, all_anchors, gt, details=None):
             tar = np.concatenate([p[1].reshape(*fm, -1, code) for p in per], axis=-2).reshape(-1, code)
             wei = np.concatenate([p[2].reshape(*fm, -1) for p in per], axis=-1).reshape(-1)
         L.append(lab), T.append(tar), W.append(wei)
+    if not L:   # B = 0: the shapes without a sample
+        n_out = sum(len(a) for a in flat)
+        return {"box_cls_labels": np.zeros((0, n_out), dtype=np.int32), "box_reg_targets": np.zeros((0, n_out, code), dtype=F),
+                "reg_weights": np.zeros((0, n_out), dtype=F)}
     return {"box_cls_labels": np.stack(L), "box_reg_targets": np.stack(T), "reg_weights": np.stack(W)}
 
 
@@ -322,7 +326,10 @@ def fixture_cases(rec):
             "IoU one float above unmatched", "IoU == unmatched", "rot one float below pi/4", "rot == pi/4", "rot one float above pi/4",
             "heading beyond +2 pi", "heading beyond -2 pi", "gt size below 1e-5", "three classes, different thresholds, single head",
             "three classes multihead, code 9 + sincos", "one class", "B = 1", "B = 2", "B = 3", "map 1 x 5 x 7", "map 1 x 33 x 40",
-            "2 x 1 anchor under a concentric 4 x 1 gt gives 0.5"]
+            "2 x 1 anchor under a concentric 4 x 1 gt gives 0.5", "a class with more than 256 gts",
+            "a tie across 256 that the lower index wins", "forced from a later tile",
+            "forced from tile 0, the argmax in a later tile", "k in {2, 4, 6} in one head",
+            "multihead classes of different row counts", "a class without a gt next to a sample with more than 256"]
     for k in keys:
         got[k] = False
     for name, cfg, gt in scenes(rec):
@@ -340,6 +347,12 @@ def fixture_cases(rec):
         hit("three classes multihead, code 9 + sincos", three and cfg["use_multihead"] and cfg["code_size"] == 9 and cfg["sincos"]
             and gt.shape[2] == 10 and anchors[0].shape[-1] == 10)
         hit("one class", len(cfg["classes"]) == 1 and len(cfg["class_names"]) == 1)
+        per_loc = sorted(a.shape[3] * a.shape[4] for a in anchors)
+        hit("k in {2, 4, 6} in one head", not cfg["use_multihead"] and per_loc == [2, 4, 6])
+        hit("multihead classes of different row counts", cfg["use_multihead"] and len({int(np.prod(a.shape[:5])) for a in anchors}) >= 3)
+        for ci in range(len(anchors)):
+            n_sel = [len(details[b][ci]["rows"]) for b in range(gt.shape[0])]
+            hit("a class without a gt next to a sample with more than 256", min(n_sel) == 0 and max(n_sel) > 256)
         anchor_names = [c["class_name"] for c in cfg["classes"]]
         for b in range(gt.shape[0]):
             g = gt[b]
@@ -362,6 +375,8 @@ def fixture_cases(rec):
                 sel = g[rows]
                 lab = assign_single(d["anchors"], sel[:, :-1], d["cids"], m, u, bool(cfg["sincos"]), out["box_reg_targets"].shape[-1])[0]
                 is_max = (iou == colmax[None, :]) & (colmax[None, :] != 0)
+                rect = nearest_bev(sel)
+                hit("a class with more than 256 gts", len(rows) > 256)
                 for j in range(len(rows)):
                     best = np.flatnonzero(is_max[:, j])
                     if d["cids"][j] == 0 and sel[j, :7].any() and colmax[j] > 0 and cfg["classes"][ci]["class_name"] == cfg["class_names"][-1]:
@@ -372,6 +387,10 @@ def fixture_cases(rec):
                     other = best[arg[best] != j]
                     hit("forced by j, argmax k != j, takes k's box",
                         len(other) and (rowmax[other] < m).any() and (lab[other] == d["cids"][arg[other]]).all() and (lab[other] > 0).any())
+                    for key, mine, ok in (("forced from a later tile", other[arg[other] < 256], j >= 256),
+                                          ("forced from tile 0, the argmax in a later tile", other[arg[other] >= 256], j < 256)):
+                        only_j = [i for i in mine if is_max[i].sum() == 1]      # nothing but j forces the anchor
+                        hit(key, ok and len(only_j) and (rowmax[only_j] < u).all() and (lab[only_j] > 0).all())
                     r = rot_of(sel[j, 6])
                     if sel[j, 3] != sel[j, 4] and colmax[j] > 0:
                         hit("rot one float below pi/4", r == np.nextafter(QUARTER, F(0)))
@@ -380,10 +399,11 @@ def fixture_cases(rec):
                     hit("heading beyond +2 pi", sel[j, 6] > 2 * np.pi and colmax[j] > 0)
                     hit("heading beyond -2 pi", sel[j, 6] < -2 * np.pi and colmax[j] > 0)
                     hit("gt size below 1e-5", (sel[j, 3:6] < TINY).any() and ((arg == j) & (lab > 0)).any())
-                    for k2 in range(j + 1, len(rows)):
-                        same = np.array_equal(nearest_bev(sel[j:j + 1]), nearest_bev(sel[k2:k2 + 1])) and sel[j, 2] != sel[k2, 2]
+                    for k2 in j + 1 + np.flatnonzero((bits(rect[j + 1:]) == bits(rect[j:j + 1])).all(axis=1)):
+                        same = sel[j, 2] != sel[k2, 2]
                         fg = (lab > 0) & (iou[:, j] == rowmax) & (iou[:, k2] == rowmax)
                         hit("same footprint, different z: the lower index wins", same and fg.any() and (arg[fg] == j).all())
+                        hit("a tie across 256 that the lower index wins", j < 256 <= k2 and same and fg.any() and (arg[fg] == j).all())
                 free = ~forced
                 hit("IoU == matched", (rowmax == m).any())
                 hit("IoU == matched, not forced", (free & (rowmax == m) & (lab > 0)).any())

@@ -24,7 +24,7 @@ def gold():
 
 def test_fixture_is_small(gold):
     assert os.path.getsize(GOLD) <= os.path.getsize(os.path.join(os.path.dirname(GOLD), "pointnet2_batch.npz"))
-    assert [n for n, _, _ in seq.scenes(gold)] == ["small", "big", "multi", "lyft"]
+    assert [n for n, _, _ in seq.scenes(gold)] == ["small", "big", "multi", "lyft", "crowd", "crowd_multi"]
 
 
 def test_restatement_reproduces_the_reference(gold):
@@ -62,7 +62,7 @@ def test_the_comparison_is_not_vacuous(gold):
 
 def test_fixture_cases(gold):
     cases = seq.fixture_cases(gold)
-    assert len(cases) >= 30
+    assert len(cases) >= 40
     assert all(cases.values()), [k for k, v in cases.items() if not v]
 
 

@@ -1,19 +1,24 @@
 """GPU: modest_amd.utils.target_assigner.AxisAlignedTargetAssigner (csrc/anchor_targets.hip)
 against the outputs recorded from the reference's own assigner (tests/golden/anchor_targets.npz) and against the numpy
 restatement tests/anchor_targets_seq.py: labels, weights and every target column bit for bit; against the reference the two
-sincos columns to the bound derived in section 7i.  A mismatch reports (sample, anchor, class) and the IoUs involved."""
+sincos columns to the bound derived in section 7i.  A mismatch reports (sample, anchor, class) and the IoUs involved.
+The cases of tests/anchor_targets_cases.py cross the kernels' constants (64 gt rows per ballot, 256 gts per LDS tile, 256
+anchors per workgroup, classes of unequal length); they also run into sentinel-filled outputs with a pre-filled workspace."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import anchor_targets_cases as cases
 import anchor_targets_seq as seq
+from modest_amd import ops
 from modest_amd.utils import target_assigner as ta
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_targets.npz")
 F = np.float32
+SENTINEL = 0x5A5A5A5A
 
 
 @pytest.fixture(scope="module")
@@ -40,7 +45,7 @@ def run(cfg, anchors, gt, assigner=None, strided=False):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-@pytest.mark.parametrize("name", ["small", "big", "multi", "lyft"])
+@pytest.mark.parametrize("name", ["small", "big", "multi", "lyft", "crowd", "crowd_multi"])
 def test_fixture_scenes(gold, name):
     cfg, gt = next((c, g) for n, c, g in seq.scenes(gold) if n == name)
     anchors = seq.make_anchors(cfg)
@@ -167,3 +172,75 @@ def test_two_calls_are_bit_identical(full):
         assert torch.equal(one[k].view(torch.int32), two[k].view(torch.int32)), k
         assert np.array_equal(one[k].cpu().numpy().view(np.uint32), full["got"][k].view(np.uint32)), k
     assert a._device_tables(at) is a._tables   # the tables are built once per list of anchor tensors
+
+
+# ---- past the kernels' constants (tests/anchor_targets_cases.py) -----------------------------------------------------------
+def sentinel_outputs(B, n_out, code, dev):
+    fill = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int32, device=dev)   # noqa: E731
+    return fill(B, n_out), fill(B, n_out, code).view(torch.float32), fill(B, n_out).view(torch.float32)
+
+
+def raw_bits(t):
+    return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("name", cases.names())
+def test_cases_against_the_restatement(name):
+    case = cases.by_name(name)
+    cfg, gt = case["cfg"], case["gt"].copy()     # the case's own array is read-only
+    ref = cases.reference(case)
+    anchors, want = ref["anchors"], ref["out"]
+    dev = torch.device("cuda")
+    a = assigner_of(cfg)
+    at = [torch.from_numpy(x).to(dev) for x in anchors]
+    gd = torch.from_numpy(gt).to(dev)
+    first = a.assign_targets(at, gd)
+    got = {k: v.cpu().numpy() for k, v in first.items()}
+    why = seq.report(got, want, cfg, anchors, gt)
+    assert not why, why
+    again = a.assign_targets(at, gd)
+    for k in first:
+        assert first[k] is not again[k] and np.array_equal(raw_bits(first[k]), raw_bits(again[k])), k
+    if gt.size:
+        why = seq.report(run(cfg, anchors, gt, strided=True), want, cfg, anchors, gt)
+        assert not why, f"a non-contiguous gt tensor\n{why}"
+    # the library call itself into sentinel outputs, the workspace pre-filled: every element written, nothing read that
+    # was not written first
+    t = a._device_tables(at)
+    B, M = gt.shape[:2]
+    nbytes = ops.anchor_targets_workspace_bytes(B, len(anchors), M)
+    for fill in (0xFF, 0x00):
+        out = sentinel_outputs(B, t["n_out"], want["box_reg_targets"].shape[-1], dev)
+        ws = torch.full((max(nbytes, 256),), fill, dtype=torch.uint8, device=dev)
+        res = ops.anchor_targets(gd, t["anchors"], t["cls"], t["thr"], t["match"], t["max_rows"], t["n_out"], a.sincos,
+                                 workspace=ws, out=out)
+        assert all(r is o for r, o in zip(res, out))
+        for r, k in zip(res, ("box_cls_labels", "box_reg_targets", "reg_weights")):
+            b = raw_bits(r)
+            assert not (b == SENTINEL).any(), f"{k}: {int((b == SENTINEL).sum())} elements never written (workspace fill {fill:#x})"
+            assert np.array_equal(b, raw_bits(first[k])), f"{k} differs with the workspace filled with {fill:#x}"
+        if B and fill:
+            assert not bool((ws[:nbytes] == fill).all()), "the workspace handed in was not the one used"
+
+
+def test_out_is_validated():
+    case = cases.by_name("columns: anchors 7, gt 8")
+    dev = torch.device("cuda")
+    a = assigner_of(case["cfg"])
+    at = [torch.from_numpy(x).to(dev) for x in cases.reference(case)["anchors"]]
+    gd = torch.from_numpy(case["gt"].copy()).to(dev)
+    t = a._device_tables(at)
+    args = (gd, t["anchors"], t["cls"], t["thr"], t["match"], t["max_rows"], t["n_out"], False)
+    B, n = gd.shape[0], t["n_out"]
+    good = sentinel_outputs(B, n, 7, dev)
+    with pytest.raises(TypeError, match="labels"):
+        ops.anchor_targets(*args, out=(good[0].float(), good[1], good[2]))
+    with pytest.raises(ValueError, match="targets has shape"):
+        ops.anchor_targets(*args, out=(good[0], good[1][:, :, :6].contiguous(), good[2]))
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.anchor_targets(*args, out=(good[0], good[1], torch.zeros((n, B), device=dev).t()))
+    with pytest.raises(ValueError, match="device"):
+        ops.anchor_targets(*args, out=(good[0].cpu(), good[1], good[2]))
+    with pytest.raises(ValueError, match="labels, targets, weights"):
+        ops.anchor_targets(*args, out=good[:2])
+    assert all((raw_bits(g) == SENTINEL).all() for g in good)      # a refused call writes nothing

@@ -7,7 +7,9 @@ two extension modules ``box_utils`` and ``iou3d_nms_utils`` pull in (``pcdet_bin
 the identity.
 
 Recorded in tests/golden/anchor_targets.npz per scene: the config as JSON (plain values), the gt tensor and the three
-outputs.  Anchors are regenerated from the config by tests/anchor_targets_seq.py:make_anchors; this tool asserts the
+outputs.  Six scenes: small, big, multi, lyft, and two crowded ones past the kernels' constants (crowd: classes of 2, 6
+and 4 anchors per location, 275 gts of one class with a tie and two forcings across position 256; crowd_multi: multihead
+classes on grids of their own, 280 gts of one class), built with the helpers of tests/anchor_targets_cases.py.  Anchors are regenerated from the config by tests/anchor_targets_seq.py:make_anchors; this tool asserts the
 regenerated anchors equal the reference generator's bit for bit.  It also asserts
   * that the numpy restatement reproduces every recorded output (the sincos columns to the derived bound),
   * that torch's CPU log of every size quotient that reaches an output equals the rounded double log (sizes are redrawn
@@ -190,7 +192,64 @@ def build_scenes(seq):
         sz = np.array((4.7, 2.1, 1.7)) * rs.uniform(0.7, 1.3, 3)
         g[0, j] = [rs.uniform(-38, 38), rs.uniform(-31, 31), rs.uniform(-1.2, 0.2), *sz, rs.uniform(-3.2, 3.2), 1 if j else 0]
     out["lyft"] = (cfg, g, set())
+    out["crowd"] = crowd_scene(seq, rs)
+    out["crowd_multi"] = crowd_multi_scene(seq, rs)
     return out
+
+
+def crowd_scene(seq, rs):
+    """the single head of tests/anchor_targets_cases.py with 2, 6 and 4 anchors per location on two heights, B = 2, M = 300:
+    275 Cyclists in sample 0 (none in sample 1), among them, by position in the class, one footprint at 250 and 260 (the
+    lower index wins across the tile boundary at 256), a gt at 270 that forces an anchor whose argmax is the gt at 30,
+    and the mirror image (40 forces, 265 is the argmax)"""
+    import anchor_targets_cases as cases
+    cfg = cases.single_cfg()
+    flats = [seq.flatten(a, False) for a in seq.make_anchors(cfg)]
+    geo = dict(sx=4.0, sy=4.0, x0=0.0, y0=-14.0, a=(1.76, 0.6), cid=3)
+    j1, k1 = cases.forcer(2, 2, k_at=1.25, k_len=1.7, **geo)
+    j2, k2 = cases.forcer(6, 5, k_at=1.25, k_len=1.7, **geo)
+    special = {250: cases.twin(4, 6, -0.25, **geo), 260: cases.twin(4, 6, 0.5, **geo), 30: k1, 270: j1, 40: j2, 265: k2}
+    taken = {(4, 6), (2, 2), (3, 2), (6, 5), (7, 5)}
+    xy = {(geo["x0"] + 4.0 * ix, geo["y0"] + 4.0 * iy) for ix, iy in taken}
+    free = [f[[(float(a[0]), float(a[1])) not in xy for a in f]] for f in flats]
+    assert all(len(f) < len(g) for f, g in zip(free, flats))
+    M = 300
+    g = np.zeros((2, M, 8), dtype=F)
+    kinds = [3] * 275 + [1] * 9 + [2] * 12 + [9] * 4
+    kinds = [kinds[i] for i in rs.permutation(M)]
+    crafted, p = set(), 0
+    for j, kind in enumerate(kinds):
+        if kind == 9:
+            continue
+        if kind == 3:
+            if p in special:
+                g[0, j] = special[p]
+                crafted.add((0, j))
+            else:
+                g[0, j] = cases.near(rs, free[2], 3, 8, far=rs.randint(3) == 0)
+            p += 1
+        else:
+            g[0, j] = cases.near(rs, free[kind - 1], kind, 8)
+    for j in range(80):
+        c = 2 if j % 4 == 0 else 1
+        g[1, j] = cases.near(rs, flats[c - 1], c, 8)
+    return cfg, g, crafted
+
+
+def crowd_multi_scene(seq, rs):
+    """the multihead of tests/anchor_targets_cases.py on grids of their own (70, 35, 1 248 and 1 000 rows), 9 columns +
+    sincos, B = 2, M = 300: 280 Cyclists in sample 0, none in sample 1"""
+    import anchor_targets_cases as cases
+    cfg = cases.multi_cfg()
+    flats = [seq.flatten(a, True) for a in seq.make_anchors(cfg)]
+    M = 300
+    g = np.zeros((2, M, 10), dtype=F)
+    kinds = [3] * 280 + [1] * 4 + [2] * 4 + [4] * 8
+    for j, i in enumerate(rs.permutation(len(kinds))):
+        g[0, j] = cases.near(rs, flats[kinds[i] - 1], kinds[i], 10, far=kinds[i] == 3 and rs.randint(5) == 0)
+    for j, c in enumerate([1, 2, 4, 4, 1, 2, 4]):
+        g[1, j] = cases.near(rs, flats[c - 1], c, 10)
+    return cfg, g, set()
 
 
 def settle_logs(seq, cfg, gt, crafted):
@@ -207,20 +266,18 @@ def settle_logs(seq, cfg, gt, crafted):
             k = int(row[-1]) - 1
             k += len(names) if k < 0 else 0
             cl = [c for c in cfg["classes"] if 0 <= k < len(names) and c["class_name"] == names[k]]
-            for c in cl:
-                for size in c["anchor_sizes"]:
-                    for d in range(3):
-                        a = max(F(size[d]), seq.TINY)
-                        for _ in range(64):
-                            q = np.array([max(row[3 + d], seq.TINY) / a], dtype=F)
-                            if torch.log(torch.from_numpy(q)).numpy()[0] == seq.f32_of_double(np.log, q)[0]:
-                                break
-                            if d < 2 and (b, j) in crafted:
-                                raise RuntimeError(f"crafted gt {b, j}: torch's log of {q[0]!r} is not the rounded double log")
-                            row[3 + d] = np.nextafter(row[3 + d], F(np.inf))
-                            nudged += 1
-                        else:
-                            raise RuntimeError("no size found")
+            sizes = [size for c in cl for size in c["anchor_sizes"]]
+            for d in range(3):      # one value must do for every anchor size of the class
+                for _ in range(64):
+                    q = np.array([max(row[3 + d], seq.TINY) / max(F(size[d]), seq.TINY) for size in sizes], dtype=F)
+                    if np.array_equal(torch.log(torch.from_numpy(q)).numpy(), seq.f32_of_double(np.log, q)):
+                        break
+                    if d < 2 and (b, j) in crafted:
+                        raise RuntimeError(f"crafted gt {b, j}: torch's log of {q!r} is not the rounded double log")
+                    row[3 + d] = np.nextafter(row[3 + d], F(np.inf))
+                    nudged += 1
+                else:
+                    raise RuntimeError("no size found")
     return nudged
 
 
