@@ -1141,6 +1141,30 @@ int modest_spconv_gather_gemm_classes(const float *in_dev, int64_t n_in, int in_
                                       const float *bias_dev, const int32_t *map_dev, int64_t n_out, const int32_t *perm_dev,
                                       const int32_t *class_start_dev, float *out_dev, void *stream);
 
+/* ---- a30 point-head target assignment (PointHeadTemplate.assign_stack_targets of OpenPCDet's point heads) ----
+ * set_ignore_flag=True, use_ball_constraint=False.  A whole stacked batch in one call: enqueue only, no context, no
+ * device allocation, no workspace, no atomics, no synchronise, nothing read back.  Every buffer [dev].
+ *   points     (n, 4) float32 [bs_idx, x, y, z], points_stride elements from row to row (>= 4); a point belongs to sample
+ *              k iff its first column equals (float)k for a k in [0, b), else to none (label 0, targets 0).  Points need
+ *              not be grouped by sample;
+ *   gt, ext    (b, m, 8) float32 [cx, cy, cz, dx, dy, dz, rz, class], each with its three strides in elements; all m rows
+ *              take part, zero rows included;
+ *   mean_size  (n_mean, 3) float32 contiguous, or NULL with n_mean = 0 for use_mean_size=False.  Class c names row c - 1,
+ *              c <= 0 wraps once as Python does; a class beyond the table reads nothing (its six size-dependent labels
+ *              are NaN; the reference asserts).
+ * idx = the lowest box of the point's sample that holds it by the predicate of a23, fg = there is one, ext = some enlarged
+ * box of the sample holds it.  Outputs, every element written:
+ *   cls_labels   (n) int64: 0; -1 where fg != ext; where fg, 1 if num_class == 1 else the class column truncated;
+ *   box_labels   (n, 8) float32 or NULL: 0 unless fg, else PointResidualCoder.encode_torch of box idx;
+ *   part_labels  (n, 3) float32 or NULL: 0 unless fg, else the point in the box's frame / (dx, dy, dz) + 0.5; the sizes
+ *                are clamped to 1e-5f iff box_labels is given (the reference's coder clamps them in place).
+ * n == 0 launches nothing; m == 0 or b == 0 writes the background values.                                               */
+int modest_point_targets(int64_t n, const float *points_dev, int64_t points_stride, int b, int m, const float *gt_dev,
+                         int64_t gt_stride_b, int64_t gt_stride_m, int64_t gt_stride_c, const float *ext_dev,
+                         int64_t ext_stride_b, int64_t ext_stride_m, int64_t ext_stride_c, const float *mean_size_dev,
+                         int n_mean, int num_class, int64_t *cls_labels_dev, float *box_labels_dev,
+                         float *part_labels_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,8 @@ SIGNATURES = {
     "modest_spconv_class_order": (C.c_int, [VP, C.c_int64, VP, VP, VP, C.c_int64, VP, VP, VP]),
     "modest_spconv_gather_gemm_classes": (C.c_int, [VP, C.c_int64, C.c_int, VP, VP, VP, C.c_int, VP, VP, C.c_int64, VP, VP,
                                                     VP, VP]),
+    "modest_point_targets": (C.c_int, [C.c_int64, VP, C.c_int64, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, VP,
+                                       C.c_int64, C.c_int64, C.c_int64, VP, C.c_int, C.c_int, VP, VP, VP, VP]),
 }
 
 _lib = None

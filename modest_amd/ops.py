@@ -1513,3 +1513,73 @@ def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Ten
                                         labels.data_ptr(), targets.data_ptr(), weights.data_ptr(), workspace.data_ptr(),
                                         workspace.numel(), _stream()), "modest_anchor_targets")
     return labels, targets, weights
+
+
+# --------------------------------------------------------------------------- point-head target assignment
+def point_targets(points: torch.Tensor, gt_boxes: torch.Tensor, extend_gt_boxes: torch.Tensor, num_class: int,
+                  mean_size: Optional[torch.Tensor] = None, want_box: bool = False, want_part: bool = False, out=None):
+    """modest_point_targets on PyTorch's current stream: enqueue only, nothing is read back.
+    points (N, 4) float32 [bs_idx, x, y, z], rows of any stride; gt_boxes and extend_gt_boxes (B, M, 8) float32, any
+    strides; mean_size (n_cls, 3) float32 contiguous, or None for a coder with use_mean_size=False.
+    -> point_cls_labels (N) int64, point_box_labels (N, 8) float32 or None, point_part_labels (N, 3) float32 or None:
+    freshly allocated, or the three entries of `out` (None where the label is not asked for; else of exactly these shapes
+    and types, contiguous, on the points' device), every element of which is written."""
+    for t, name in ((points, "points"), (gt_boxes, "gt_boxes"), (extend_gt_boxes, "extend_gt_boxes")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError(f"points has shape {tuple(points.shape)}, expected (N, 4)")
+    if gt_boxes.ndim != 3 or gt_boxes.shape[2] != 8 or tuple(extend_gt_boxes.shape) != tuple(gt_boxes.shape):
+        raise ValueError(f"gt_boxes has shape {tuple(gt_boxes.shape)} and extend_gt_boxes {tuple(extend_gt_boxes.shape)}: "
+                         f"expected (B, M, 8) twice")
+    dev = points.device
+    if gt_boxes.device != dev or extend_gt_boxes.device != dev:
+        raise ValueError("points, gt_boxes and extend_gt_boxes are on different devices")
+    n_mean = 0
+    if mean_size is not None:
+        if not torch.is_tensor(mean_size) or not mean_size.is_cuda or mean_size.device != dev:
+            raise ValueError("mean_size must be a device tensor on the points' device")
+        if mean_size.dtype != torch.float32 or mean_size.ndim != 2 or mean_size.shape[1] != 3 or mean_size.shape[0] == 0 \
+                or not mean_size.is_contiguous():
+            raise ValueError("mean_size must be a contiguous (n_cls, 3) float32 tensor with n_cls >= 1")
+        n_mean = int(mean_size.shape[0])
+    if int(num_class) < 1:
+        raise ValueError(f"num_class is {num_class}")
+    N = int(points.shape[0])
+    B, M = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+    if points.stride(1) != 1:
+        points = points.contiguous()
+    want = (("point_cls_labels", torch.int64, (N,), True), ("point_box_labels", torch.float32, (N, 8), bool(want_box)),
+            ("point_part_labels", torch.float32, (N, 3), bool(want_part)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if asked else None for _, dtype, shape, asked in want)
+    if len(out) != 3:
+        raise ValueError("out must be (point_cls_labels, point_box_labels, point_part_labels)")
+    for t, (name, dtype, shape, asked) in zip(out, want):
+        if not asked:
+            if t is not None:
+                raise ValueError(f"out {name} is given but not asked for")
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"out {name} is missing")
+        _dev(t, dtype, f"out {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.device != dev:
+            raise ValueError(f"out {name} is on {t.device}, points on {dev}")
+    labels, box, part = out
+    if N == 0:
+        return labels, box, part   # nothing to write, nothing launched
+    lib = load()
+    gs = [int(v) for v in gt_boxes.stride()] if B and M else [0, 0, 0]
+    es = [int(v) for v in extend_gt_boxes.stride()] if B and M else [0, 0, 0]
+    with torch.cuda.device(dev):
+        check(lib.modest_point_targets(N, points.data_ptr(), int(points.stride(0)) if N > 1 else 4, B, M,
+                                       gt_boxes.data_ptr() if B and M else None, *gs,
+                                       extend_gt_boxes.data_ptr() if B and M else None, *es,
+                                       mean_size.data_ptr() if n_mean else None, n_mean, int(num_class), labels.data_ptr(),
+                                       box.data_ptr() if box is not None else None,
+                                       part.data_ptr() if part is not None else None, _stream()), "modest_point_targets")
+    return labels, box, part

@@ -29,6 +29,11 @@ instead of the module whose ``forward`` / ``backward`` are not provided.  A modu
 ``install(sparse_inverse=True)`` binds ``modest_amd.utils.spconv_inverse`` -- ``modest_amd.utils.spconv`` plus
 ``SparseInverseConv3d``, what PartA2's ``UNetV2`` is built from -- as ``spconv``, in place of the
 stand-in or of ``modest_amd.utils.spconv``; an installed or imported spconv is left alone.
+
+``install(point_targets=True)`` sets ``modest_amd.utils.point_head_targets.assign_stack_targets`` -- the target assignment
+of the point heads in one call -- on ``PointHeadTemplate`` of
+``pcdet.models.dense_heads.point_head_template``, which is imported for it if it is not yet (after every other binding,
+so that the import finds the shims).  Where that module cannot be imported nothing is bound.
 """
 import importlib
 import importlib.util
@@ -54,6 +59,8 @@ ANCHOR_TARGETS_NAME = "pcdet.models.dense_heads.target_assigner.axis_aligned_tar
 ANCHOR_TARGETS = "modest_amd.utils.target_assigner"   # bound to ANCHOR_TARGETS_NAME by install(anchor_targets=True)
 ROIAWARE_NAME = "pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"
 ROIAWARE_POOL = "modest_amd.utils.roiaware_voxel_pool_cuda"   # bound to ROIAWARE_NAME by install(roiaware_pool=True)
+POINT_TARGETS_NAME = "pcdet.models.dense_heads.point_head_template"
+POINT_TARGETS = "modest_amd.utils.point_head_targets"   # its method set on PointHeadTemplate by install(point_targets=True)
 
 
 class StandIn(types.ModuleType):
@@ -129,8 +136,24 @@ def _bind_roiaware_pool(before):
     return ours
 
 
+def _bind_point_targets():
+    """PointHeadTemplate.assign_stack_targets := ours, in the reference's module if it is imported or can be
+    -> that module, or None"""
+    mod = sys.modules.get(POINT_TARGETS_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(POINT_TARGETS_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    head = getattr(mod, "PointHeadTemplate", None)
+    if head is None:
+        return None
+    importlib.import_module(POINT_TARGETS).bind(head)
+    return mod
+
+
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
-            sparse_inverse=False):
+            sparse_inverse=False, point_targets=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     roiaware_before = sys.modules.get(ROIAWARE_NAME)
@@ -167,4 +190,8 @@ def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets
             utils = importlib.import_module(SPCONV_UTILS)
             spconv.utils = utils
             sys.modules["spconv.utils"] = utils   # `from spconv.utils import ...`: a stand-in has no __path__ to search
+    if point_targets:
+        mod = _bind_point_targets()
+        if mod is not None:
+            bound[POINT_TARGETS_NAME] = mod
     return bound
