@@ -4,8 +4,11 @@ tests/test_gpu_point_targets.py runs them on the device against tests/point_targ
 
 A case is a dict: points (N, 4), gt and ext (B, M, 8), num_class, mean (n_cls, 3) or None, want_box, want_part, and
 ``present``: a function of the case that says, from the inputs alone (through the restatement), whether the edge is there.
-All cases keep B <= 3, N <= ~1500 and M <= one tile + 1.
+The cases of CASES keep B <= 3, N <= ~1500 and M <= one tile + 1; those of PAST go on from there: up to 40 samples, four
+tiles and 20 100 points, where the kernel's tile loop and round loop repeat.  ``past(name)`` builds a PAST case once
+per process and hands out the same dict (nobody writes into it).
 """
+import functools
 import os
 import re
 
@@ -338,3 +341,259 @@ CASES = {
     **{f"want_box {b}, want_part {p}": (lambda b=b, p=p: wants(b, p)) for b in (False, True) for p in (False, True)},
     "grouped, three samples": grouped_big,
 }
+
+
+# ------------------------------------------------------------------------- past 65 boxes, 3 samples and one workgroup
+def held(c, s):
+    """(rows of sample s holding each of its points (M, n) bool, the indices of those points)"""
+    sel = np.flatnonzero(seq.sample_of(c["points"], c["gt"].shape[0]) == s)
+    return roipool_seq.inside_mask(c["points"][sel, 1:4], np.ascontiguousarray(c["gt"][s, :, :7])), sel
+
+
+def first_enlarged(c):
+    """(N,) the lowest enlarged row of the point's sample holding it, -1 for none"""
+    k = seq.sample_of(c["points"], c["gt"].shape[0])
+    out = np.full(len(k), -1, dtype=np.int64)
+    for s in range(c["gt"].shape[0]):
+        sel = np.flatnonzero(k == s)
+        out[sel] = roipool_seq.points_in_boxes(np.ascontiguousarray(c["ext"][s:s + 1, :, :7]), c["points"][None, sel, 1:4])[0]
+    return out
+
+
+def margin_point(gt, b, j, rs):
+    """5 cm outside box j of sample b across an x face: inside the box grown by 20 cm only"""
+    g = gt[b, j]
+    u = np.array([[(0.5 + 0.05 / g[3]) * rs.choice([-1, 1]), rs.uniform(-0.4, 0.4), rs.uniform(-0.4, 0.4)]])
+    return [b, *local_to_world(g, u)[0]]
+
+
+def grown(g, by):
+    """a copy of row g with every size grown by `by` metres and the next class"""
+    out = g.copy()
+    out[3:6] += F(by)
+    out[7] = 1 + g[7] % 3
+    return out
+
+
+def two_tiles():
+    M = 2 * TILE
+    pts, gt = random_scene(30, 2, M, 600, live=[M, M])
+    gt[:, M - 1, 0] += F(200.0)              # the last row lies alone: no lower row takes its points
+    rs = np.random.RandomState(30)
+    pts[290:300] = [inside_point(gt, 0, M - 1, u) for u in rs.uniform(-0.45, 0.45, (10, 3))]
+    pts[0:5] = [inside_point(gt, 0, 0, u) for u in rs.uniform(-0.45, 0.45, (5, 3))]
+
+    def present(c):
+        _, idx, _, lab = state(c)
+        return c["gt"].shape[1] == 2 * TILE and bool(c["gt"][:, :, 3:6].all()) and (idx[290:300] == 2 * TILE - 1).all() \
+            and (idx[0:5] == 0).all() and (lab[290:300] > 0).all() and set(idx[idx >= 0] // TILE) == {0, 1}
+    return case(pts, gt, present)
+
+
+def two_tiles_and_a_row():
+    M = 2 * TILE + 1
+    pts, gt = random_scene(31, 2, M, 500, live=[M, M])
+    gt[:, M - 1, 0] += F(300.0)
+    pts[400:412] = [inside_point(gt, 1, M - 1, u) for u in np.random.RandomState(31).uniform(-0.45, 0.45, (12, 3))]
+
+    def present(c):
+        k, idx, _, _ = state(c)
+        m, sel = held(c, 1)
+        only = sel[m[2 * TILE] & ~m[:2 * TILE].any(axis=0)]
+        return c["gt"].shape[1] == 2 * TILE + 1 and len(only) >= 10 and (idx[only] == 2 * TILE).all() \
+            and set(idx[idx >= 0] // TILE) == {0, 1, 2}
+    return case(pts, gt, present)
+
+
+def three_tiles_and_37():
+    M = 3 * TILE + 37
+    pts, gt = random_scene(32, 2, M, 1500, live=[M, M])
+
+    def present(c):
+        idx = state(c)[1]
+        return c["gt"].shape[1] == 3 * TILE + 37 and set(idx[idx >= 0] // TILE) == {0, 1, 2, 3} \
+            and bool((idx >= 3 * TILE + 32).any())
+    return case(pts, gt, present)
+
+
+def first_hit_wins_across_tiles():
+    M = 2 * TILE + 20
+    a, b, c_ = 5, TILE + 9, 2 * TILE + 3
+    pts, gt = random_scene(33, 2, M, 800, live=[M, M])
+    gt[1, a, 0:2] = [150.0, 150.0]           # away from every other box
+    gt[1, b] = grown(gt[1, a], 0.5)
+    gt[1, c_] = grown(gt[1, b], 0.5)
+    rs = np.random.RandomState(33)
+    pts[600:610] = [inside_point(gt, 1, a, u) for u in rs.uniform(-0.45, 0.45, (10, 3))]
+    for i in range(610, 620):                # 15 cm outside row a, 10 cm inside row b
+        u = [(0.5 + 0.15 / gt[1, a, 3]) * rs.choice([-1, 1]), rs.uniform(-0.4, 0.4), rs.uniform(-0.4, 0.4)]
+        pts[i] = inside_point(gt, 1, a, u)
+
+    def present(c):
+        _, idx, _, lab = state(c)
+        g = c["gt"]
+        m, sel = held(c, 1)
+        three, two = sel[m[a] & m[b] & m[c_]], sel[~m[a] & m[b] & m[c_]]
+        across = 0
+        for s in range(2):
+            ms = held(c, s)[0]
+            across += int((sum(ms[t:t + TILE].any(axis=0).astype(int) for t in range(0, M, TILE)) >= 2).sum())
+        return len({int(g[1, a, 7]), int(g[1, b, 7]), int(g[1, c_, 7])}) == 3 and a < TILE <= b < 2 * TILE <= c_ \
+            and len(three) >= 10 and (idx[three] == a).all() and (lab[three] == int(g[1, a, 7])).all() \
+            and len(two) >= 10 and (idx[two] == b).all() and (lab[two] == int(g[1, b, 7])).all() and across >= 30
+    return case(pts, gt, present)
+
+
+def enlarged_rows_elsewhere():
+    M = 2 * TILE + 11
+    pts, gt = random_scene(34, 2, M, 1400, live=[M, M])
+    order = np.roll(np.arange(M), TILE + 7)
+    ext = seq.enlarge(gt)[:, order]
+    ext[1, :, 0] += F(500.0)                 # sample 1: no enlarged row near any point
+
+    def present(c):
+        k, idx, hit, lab = state(c)
+        fe = first_enlarged(c)
+        ign = (k == 0) & (idx < 0) & (fe >= 0)
+        per_tile = [int((fe[ign] // TILE == t).sum()) for t in range(3)]
+        apart = (k == 0) & (idx >= 0) & (fe >= 0) & (idx // TILE != fe // TILE)
+        one = (k == 1) & (idx >= 0)
+        return seq.same_bits(c["ext"][0], seq.enlarge(c["gt"])[0, order]) and min(per_tile) >= 3 and (lab[ign] == -1).all() \
+            and int(apart.sum()) >= 10 and int(one.sum()) >= 10 and not hit[k == 1].any() and (lab[one] > 0).all() \
+            and (lab[one] == c["gt"][1, idx[one], 7].astype(np.int64)).all()
+    return case(pts, gt, present, ext=ext)
+
+
+def sixteen_samples_in_one_workgroup():
+    pts, gt = random_scene(35, 16, 6, WG, live=[4] * 16)
+    rs = np.random.RandomState(35)
+    for b in range(16):
+        pts[16 * b] = inside_point(gt, b, 0)
+        pts[16 * b + 1] = margin_point(gt, b, 0, rs)
+
+    def present(c):
+        k, idx, _, lab = state(c)
+        return len(k) == WG and (k == np.arange(WG) // 16).all() \
+            and all((idx[k == b] >= 0).any() and (lab[k == b] == -1).any() for b in range(16))
+    return case(pts, gt, present)
+
+
+def forty_samples_shuffled():
+    B, M = 40, TILE + 3
+    pts, gt = random_scene(36, B, M, 520, live=[M] * B)
+    for b in range(B):
+        j = TILE + b % 3
+        gt[b, j, 0] += F(200.0)
+        pts[13 * b] = inside_point(gt, b, j)                 # a foreground point of every sample, past the first tile
+    pts = pts[np.random.RandomState(36).permutation(len(pts))]
+
+    def present(c):
+        k, idx, _, _ = state(c)
+        full = [len(set(k[i:i + 64])) for i in range(0, len(k) - 63, 64)]     # 520 = 8 wavefronts of 64 and 8 points
+        return c["gt"].shape[:2] == (40, TILE + 3) and len(k) == 520 and len(full) == 8 and min(full) >= 20 \
+            and set(k[idx >= 0]) == set(range(40)) and bool((idx >= TILE).any()) and len(set(k[512:])) >= 2
+    return case(pts, gt, present)
+
+
+def samples_descending():
+    pts, gt = random_scene(37, 5, 12, 1500, live=[10] * 5)
+    count = {4: 300, 3: 212, 2: 60, 1: 60, 0: 68}            # 700 points: workgroups of one, two and three samples
+    pts = pts[np.concatenate([np.flatnonzero(pts[:, 0] == s)[:count[s]] for s in (4, 3, 2, 1, 0)])]
+
+    def present(c):
+        k, idx, _, _ = state(c)
+        per = [len(set(k[i:i + WG])) for i in range(0, len(k), WG)]
+        return len(k) == 700 and (np.diff(k) <= 0).all() and k[0] == 4 and k[-1] == 0 and 1 in per and 2 in per \
+            and set(k[idx >= 0]) == {0, 1, 2, 3, 4}
+    return case(pts, gt, present)
+
+
+def samples_no_point_names():
+    pts, gt = random_scene(38, 9, 8, 900, live=[6] * 9)
+    pts = pts[np.isin(pts[:, 0], (1, 4, 8))]                 # 100 points each of samples 1, 4 and 8
+    gt[4, 6] = grown(gt[1, 2], 0.5)                          # sample 4 has a row around a box of sample 1, and the reverse
+    gt[1, 6] = grown(gt[4, 3], 0.5)
+    rs = np.random.RandomState(38)
+    pts[10:35] = [inside_point(gt, 1, 2, u) for u in rs.uniform(-0.45, 0.45, (25, 3))]
+    pts[110:135] = [inside_point(gt, 4, 3, u) for u in rs.uniform(-0.45, 0.45, (25, 3))]
+    gt[0], gt[2], gt[3] = gt[4], gt[8], gt[1]                # the rows a sample renumbered by rank would read
+
+    def present(c):
+        k, idx, _, _ = state(c)
+        g, p = c["gt"], c["points"]
+
+        def misled(s, other):
+            """points of sample s that `other`'s rows hold too, in a row that differs from the one s gives them"""
+            sel = np.flatnonzero((k == s) & (idx >= 0))
+            m = roipool_seq.inside_mask(p[sel, 1:4], np.ascontiguousarray(g[other, :, :7]))
+            there = m.any(axis=0)
+            differ = (g[other, m.argmax(axis=0)] != g[s, idx[sel]]).any(axis=1)
+            return int((there & differ).sum())
+        return g.shape[0] == 9 and set(k) == {1, 4, 8} and np.array_equal(g[0], g[4]) and np.array_equal(g[2], g[8]) \
+            and np.array_equal(g[3], g[1]) and misled(1, 0) >= 20 and misled(4, 1) >= 20
+    return case(pts, gt, present)
+
+
+STRAYS = (-1.0, 2.0, 0.5, np.nan)
+
+
+def strays_by_the_wavefront():
+    N = 3 * WG + 64
+    pts, gt = random_scene(39, 2, 8, N, live=[6, 6])
+    rs = np.random.RandomState(39)
+    for i in list(range(64, 128)) + list(range(WG, 2 * WG)):
+        pts[i] = [STRAYS[i % 4], *inside_point(gt, 0, i % 6, rs.uniform(-0.4, 0.4, 3))[1:]]
+
+    def present(c):
+        k, _, _, lab = state(c)
+        p = c["points"]
+        stray = np.zeros(len(p), dtype=bool)
+        stray[64:128] = stray[WG:2 * WG] = True
+        would = roipool_seq.inside_mask(p[:, 1:4], np.ascontiguousarray(c["gt"][0, :, :7])).any(axis=0)
+        seen = [bool((p[stray, 0] == F(v)).any()) for v in STRAYS[:3]] + [bool(np.isnan(p[stray, 0]).any())]
+        return len(p) == 3 * WG + 64 and c["gt"].shape[0] == 2 and (k[stray] == -1).all() and (k[~stray] >= 0).all() \
+            and would[stray].all() and (lab[stray] == 0).all() and all(seen) and bool((lab[~stray] > 0).any())
+    return case(pts, gt, present)
+
+
+def one_point_in_the_tail_workgroup():
+    N, M = 4 * WG + 1, TILE + 10
+    pts, gt = random_scene(40, 3, M, N, live=[M] * 3)
+    gt[2, TILE + 5, 0] += F(200.0)
+    pts[-1] = inside_point(gt, 2, TILE + 5)
+
+    def present(c):
+        k, idx, _, lab = state(c)
+        return len(k) == 4 * WG + 1 and k[-1] == c["gt"].shape[0] - 1 and idx[-1] == TILE + 5 and lab[-1] > 0
+    return case(pts, gt, present)
+
+
+def detector_sized():
+    B, M, per = 4, 200, 5003
+    pts, gt = random_scene(41, B, M, B * per, live=[200, 137, 65, 0])
+    pts[-1] = [3, 0, 0, 0]                   # the origin, in a sample of zero rows only
+
+    def present(c):
+        k, idx, _, lab = state(c)
+        return c["gt"].shape[:2] == (4, 200) and [int((k == s).sum()) for s in range(4)] == [5003] * 4 \
+            and not c["gt"][3].any() and k[-1] == 3 and idx[-1] == 0 and bool((idx >= 2 * TILE).any()) \
+            and bool((lab == -1).any()) and -(-len(k) // WG) >= 70
+    return case(pts, gt, present)
+
+
+PAST = {
+    "M = 2 tiles": two_tiles, "M = 2 tiles + 1": two_tiles_and_a_row, "M = 3 tiles + 37": three_tiles_and_37,
+    "first hit wins across tiles": first_hit_wins_across_tiles, "enlarged rows elsewhere": enlarged_rows_elsewhere,
+    "16 samples in one workgroup": sixteen_samples_in_one_workgroup,
+    "40 samples shuffled, two tiles": forty_samples_shuffled, "samples descending": samples_descending,
+    "samples that no point names": samples_no_point_names,
+    "a wavefront and a workgroup of strays": strays_by_the_wavefront,
+    "one point in the tail workgroup": one_point_in_the_tail_workgroup, "detector-sized": detector_sized,
+}
+
+
+@functools.lru_cache(maxsize=None)
+def past(name):
+    """the PAST case `name` with its restatement result under "want", built once: shared, so leave it unchanged"""
+    c = PAST[name]()
+    return dict(c, want=run(c))

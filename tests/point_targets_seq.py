@@ -60,6 +60,65 @@ def membership(points, gt, ext):
     return k, idx, hit
 
 
+# the faults membership_tiled can be asked for: each is a way the kernel's walk could be wrong that changes an output
+FAULTS = ("tile index restarts", "last tile wins", "enlarged latch per tile", "three rounds only",
+          "rounds in order of appearance", "sample by rank among those present", "minimum of the first wavefront only",
+          "strays join sample 0")
+
+
+def membership_tiled(points, gt, ext, wg, tile, fault=None):
+    """membership, walked as csrc/point_targets.hip walks: workgroups of `wg` points; in each, rounds on the lowest sample
+    not yet served; in each round, tiles of `tile` rows of the sample's gt and enlarged boxes; idx is kept on the first
+    hit, the enlarged latch is never reset.  `fault` (one of FAULTS) breaks the walk in the named way:
+      tile index restarts                  the row index of a hit is min(j0, tile) + j: right in the first two tiles only
+      last tile wins                       a later tile's first hit overwrites idx
+      enlarged latch per tile              the enlarged latch is cleared at the start of every tile
+      three rounds only                    a workgroup stops after three rounds
+      rounds in order of appearance        a round serves the first lane's sample above `done`, not the lowest
+      sample by rank among those present   the box rows are taken at the sample's rank among the samples the batch names
+      minimum of the first wavefront only  the round's sample is not reduced across the workgroup's wavefronts
+      strays join sample 0                 a point that names no sample is tested against sample 0
+    -> (k, idx, ext_hit) as membership: k is the point's sample whatever the fault"""
+    assert fault is None or fault in FAULTS, fault
+    points = np.asarray(points, dtype=F)
+    B, M, N = gt.shape[0], gt.shape[1], len(points)
+    k = sample_of(points, B)
+    kk = k.copy()
+    if fault == "strays join sample 0" and B:
+        kk[k < 0] = 0
+    named = np.unique(kk[kk >= 0])
+    idx = np.full(N, -1, dtype=np.int64)
+    hit = np.zeros(N, dtype=bool)
+    for w0 in range(0, N if M else 0, wg):
+        lanes = np.arange(w0, min(w0 + wg, N))
+        kw = kk[lanes]
+        done, rounds = -1, 0
+        while True:
+            left = kw > done
+            pool = kw[:64][left[:64]] if fault == "minimum of the first wavefront only" else kw[left]
+            if len(pool) == 0 or (fault == "three rounds only" and rounds == 3):
+                break
+            s = int(pool[0] if fault == "rounds in order of appearance" else pool.min())
+            rounds += 1
+            row = int(np.searchsorted(named, s)) if fault == "sample by rank among those present" else s
+            mine = lanes[kw == s]
+            xyz = points[mine, 1:4]
+            for j0 in range(0, M, tile):
+                cnt = min(tile, M - j0)
+                if fault == "enlarged latch per tile":
+                    hit[mine] = False
+                g = roipool_seq.inside_mask(xyz, np.ascontiguousarray(gt[row, j0:j0 + cnt, :7]))
+                e = roipool_seq.inside_mask(xyz, np.ascontiguousarray(ext[row, j0:j0 + cnt, :7]))
+                take = g.any(axis=0)
+                if fault != "last tile wins":
+                    take &= idx[mine] < 0
+                base = min(j0, tile) if fault == "tile index restarts" else j0
+                idx[mine[take]] = base + g.argmax(axis=0)[take]
+                hit[mine] |= e.any(axis=0)
+            done = s
+    return k, idx, hit
+
+
 def encode(box, xyz, cls, mean_size):
     """PointResidualCoder.encode_torch: box (n, 7), xyz (n, 3), cls (n,) int64, mean_size (n_cls, 3) or None -> (n, 8)"""
     box, xyz = np.asarray(box, dtype=F), np.asarray(xyz, dtype=F)
@@ -105,11 +164,12 @@ def part_offsets(box, xyz, clamped):
     return out
 
 
-def assign(points, gt, ext, num_class, mean_size=None, want_box=False, want_part=False):
-    """-> dict(point_cls_labels (N) int64, point_box_labels (N, 8) float32 or None, point_part_labels (N, 3) or None)"""
+def assign(points, gt, ext, num_class, mean_size=None, want_box=False, want_part=False, member=None):
+    """-> dict(point_cls_labels (N) int64, point_box_labels (N, 8) float32 or None, point_part_labels (N, 3) or None);
+    `member`: the (k, idx, ext_hit) to label from in place of membership's (what membership_tiled returns)"""
     points, gt, ext = (np.asarray(a, dtype=F) for a in (points, gt, ext))
     N = len(points)
-    k, idx, hit = membership(points, gt, ext)
+    k, idx, hit = membership(points, gt, ext) if member is None else member
     fg = idx >= 0
     rows = gt[k[fg], idx[fg]] if fg.any() else np.zeros((0, 8), dtype=F)
     with np.errstate(invalid="ignore"):
@@ -244,4 +304,31 @@ def fixture_cases(rec):
             got["class 0 wraps"] |= cfg["use_mean_size"] and cfg["want_box"] and cfg["num_class"] > 1 and bool((rows[:, 7] == 0).any())
             got["a size at the clamp"] |= cfg["want_box"] and bool((rows[:, 3:6] < TINY).any())
             got["zero row holds the origin"] |= bool((~rows.any(axis=1)).any())
+    return got
+
+
+def crowd_cases(rec, tile):
+    """name -> bool for what the scene `crowd` (tests/golden/point_targets_crowd.npz) promises past one tile of `tile` rows,
+    read from its recorded arrays alone"""
+    cfg, pts, gt, ext, _ = scene_inputs(rec, "crowd")
+    lab = recorded(rec, "crowd")["point_cls_labels"]
+    k, idx, hit = membership(pts, gt, ext)
+    M = gt.shape[1]
+    last = (M - 1) // tile * tile              # the first row of the last tile
+    got = {"idx in each of three tiles": last == 2 * tile and set(idx[idx >= 0] // tile) == {0, 1, 2},
+           "rows of two tiles hold a point, the lower row wins": False,
+           "ignored, the only enlarged hit in the last tile": False,
+           "point of no sample": bool((k < 0).any()) and bool((lab[k < 0] == 0).all())}
+    for s in range(gt.shape[0]):
+        sel = np.flatnonzero(k == s)
+        g = roipool_seq.inside_mask(pts[sel, 1:4], np.ascontiguousarray(gt[s, :, :7]))
+        e = roipool_seq.inside_mask(pts[sel, 1:4], np.ascontiguousarray(ext[s, :, :7]))
+        tiles = np.stack([g[t:t + tile].any(axis=0) for t in range(0, M, tile)])
+        two = tiles.sum(axis=0) >= 2
+        first = g.argmax(axis=0)
+        got["rows of two tiles hold a point, the lower row wins"] |= bool(two.any()) and bool(
+            (idx[sel][two] == first[two]).all() and (lab[sel][two] == gt[s, first[two], 7].astype(np.int64)).all()
+            and (first[two] // tile == tiles[:, two].argmax(axis=0)).all())
+        only = (idx[sel] < 0) & e[last:].any(axis=0) & ~e[:last].any(axis=0)
+        got["ignored, the only enlarged hit in the last tile"] |= bool(only.any()) and bool((lab[sel][only] == -1).all())
     return got

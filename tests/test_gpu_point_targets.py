@@ -3,7 +3,10 @@ against the numpy restatement tests/point_targets_seq.py, bit for bit (a NaN equ
 tests/point_targets_cases.py -- each asserts from its inputs that the edge it is named after is present -- and against the
 outputs recorded from the reference's own assign_stack_targets (tests/golden/point_targets.npz): labels and box labels
 bit for bit, part labels within the bound section 7l derives from the inputs.  Every case also runs into outputs filled
-with a sentinel (none survives), twice (identical bits) and through a non-contiguous gt tensor."""
+with a sentinel (none survives), twice (identical bits) and through a non-contiguous gt tensor.  The cases of PAST (past
+two and three tiles of boxes, up to 40 rounds in a workgroup, samples nobody names, 79 workgroups) run the same checks
+and four layouts in which the gt and the enlarged boxes differ in every stride; the scene of
+tests/golden/point_targets_crowd.npz (140 rows) runs with the five of the first fixture."""
 import os
 import types
 
@@ -18,6 +21,7 @@ from modest_amd.utils import point_head_targets as pht
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "point_targets.npz")
+GOLD_CROWD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "point_targets_crowd.npz")
 F = np.float32
 KEYS = ("point_cls_labels", "point_box_labels", "point_part_labels")
 
@@ -25,6 +29,11 @@ KEYS = ("point_cls_labels", "point_box_labels", "point_part_labels")
 @pytest.fixture(scope="module")
 def gold():
     return dict(np.load(GOLD))
+
+
+@pytest.fixture(scope="module")
+def crowd():
+    return dict(np.load(GOLD_CROWD))
 
 
 def strided_copy(t):
@@ -93,14 +102,95 @@ def test_cases_against_the_restatement(name):
     assert not why, "a non-contiguous gt tensor\n" + "\n".join(why)
 
 
-def test_fixture_scenes(gold):
-    for name in seq.scenes(gold):
-        cfg, pts, gt, ext, mean = seq.scene_inputs(gold, name)
+def call(c, pts, gt, ext, mean, out=None):
+    return ops.point_targets(pts, gt, ext, c["num_class"], mean_size=mean, want_box=c["want_box"], want_part=c["want_part"],
+                             out=out)
+
+
+@pytest.mark.parametrize("name", list(cases.PAST))
+def test_past_the_tile_against_the_restatement(name):
+    c = cases.past(name)
+    want = c["want"]
+    pts, gt, ext, mean = device_inputs(c)
+    got = to_host(call(c, pts, gt, ext, mean))
+    why = seq.mismatches(got, want)
+    assert not why, "against the restatement\n" + "\n".join(why)
+
+
+@pytest.mark.parametrize("name", list(cases.PAST))
+def test_past_the_tile_into_given_outputs_and_twice(name):
+    c = cases.past(name)
+    want = c["want"]
+    pts, gt, ext, mean = device_inputs(c)
+    out = sentinel_outputs(c)
+    res = call(c, pts, gt, ext, mean, out=out)
+    assert all(a is b for a, b in zip(res, out))
+    first = to_host(res)
+    assert not seq.mismatches(first, want), "into given outputs"
+    assert not (first["point_cls_labels"] == 0x5A5A5A5A5A5A5A5A).any()
+    for k in KEYS[1:]:
+        assert not (seq.bits(first[k]) == 0x5A5A5A5A).any(), k
+    again = to_host(call(c, pts, gt, ext, mean))
+    for k in KEYS:   # two runs: identical bytes, NaN payloads included
+        assert first[k].tobytes() == again[k].tobytes(), k
+
+
+def permuted_copy(t, order):
+    """t (B, M, 8) stored with its dimensions in `order` (a permutation of 0, 1, 2), as a view of shape (B, M, 8)"""
+    stored = t.permute(*order).contiguous()
+    view = stored.permute(*[order.index(d) for d in range(3)])
+    assert view.shape == t.shape and torch.equal(view, t)
+    return view
+
+
+LAYOUTS = {
+    "gt contiguous, ext strided": (lambda t: t.contiguous(), strided_copy),
+    "gt strided, ext contiguous": (strided_copy, lambda t: t.contiguous()),
+    "gt as (8, B, M), ext as (M, 8, B)": (lambda t: permuted_copy(t, (2, 0, 1)), lambda t: permuted_copy(t, (1, 2, 0))),
+    "gt as (M, 8, B), ext as (8, B, M)": (lambda t: permuted_copy(t, (1, 2, 0)), lambda t: permuted_copy(t, (2, 0, 1))),
+}
+
+
+@pytest.mark.parametrize("name", list(cases.PAST))
+def test_past_the_tile_with_unequal_box_strides(name):
+    c = cases.past(name)
+    pts, gt, ext, mean = device_inputs(c)
+    for layout, (lay_gt, lay_ext) in LAYOUTS.items():
+        g, e = lay_gt(gt), lay_ext(ext)
+        assert all(a != b for a, b in zip(g.stride(), e.stride())), (layout, g.stride(), e.stride())
+        why = seq.mismatches(to_host(call(c, pts, g, e, mean)), c["want"])
+        assert not why, layout + "\n" + "\n".join(why)
+
+
+def test_the_same_boxes_for_every_sample():
+    """a batch stride of 0: gt one (1, M, 8) tensor expanded over B samples beside a materialised enlargement, then the
+    enlarged boxes expanded beside a materialised gt"""
+    B, M = 4, 2 * cases.TILE + 5
+    pts, one = cases.random_scene(50, 1, M, 1200, live=[M])
+    pts[:, 0] = np.arange(len(pts)) * B // len(pts)                 # the same boxes, four samples' points
+    gt = np.ascontiguousarray(np.broadcast_to(one, (B, M, 8)))
+    c = cases.case(pts, gt, None)
+    want = cases.run(c)
+    k, idx, hit = seq.membership(c["points"], c["gt"], c["ext"])
+    assert set(k[idx >= 0]) == set(range(B)) and set(idx[idx >= 0] // cases.TILE) == {0, 1, 2} and bool((hit & (idx < 0)).any())
+    dev = torch.device("cuda")
+    p, mean = torch.from_numpy(c["points"]).to(dev), torch.from_numpy(c["mean"]).to(dev)
+    g1, e1 = torch.from_numpy(c["gt"][:1]).to(dev), torch.from_numpy(c["ext"][:1]).to(dev)
+    g, e = torch.from_numpy(c["gt"]).to(dev), torch.from_numpy(c["ext"]).to(dev)
+    for gt_t, ext_t in ((g1.expand(B, M, 8), e), (g, e1.expand(B, M, 8))):
+        assert 0 in (gt_t.stride(0), ext_t.stride(0)) and gt_t.stride(0) != ext_t.stride(0)
+        why = seq.mismatches(to_host(call(c, p, gt_t, ext_t, mean)), want)
+        assert not why, "\n".join(why)
+
+
+def test_fixture_scenes(gold, crowd):
+    for rec, name in [(rec, name) for rec in (gold, crowd) for name in seq.scenes(rec)]:
+        cfg, pts, gt, ext, mean = seq.scene_inputs(rec, name)
         c = dict(points=pts, gt=gt, ext=ext, num_class=cfg["num_class"], mean=mean, want_box=cfg["want_box"],
                  want_part=cfg["want_part"])
         got = run(c)
         bound = seq.part_bound(pts, gt, ext, cfg["want_box"]) if cfg["want_part"] else None
-        why = seq.mismatches(got, seq.recorded(gold, name), bound=bound)
+        why = seq.mismatches(got, seq.recorded(rec, name), bound=bound)
         assert not why, f"{name} against the reference\n" + "\n".join(why)
         why = seq.mismatches(got, cases.run(c))
         assert not why, f"{name} against the restatement\n" + "\n".join(why)
@@ -150,6 +240,13 @@ def test_points_rows_may_be_strided():
     _, gt, ext, mean = device_inputs(c)
     view = wide[:, :4]
     assert not view.is_contiguous()
+    got = to_host(ops.point_targets(view, gt, ext, 3, mean_size=mean, want_box=True, want_part=True))
+    assert not seq.mismatches(got, cases.run(c))
+    # columns two elements apart: the wrapper hands the kernel a contiguous copy
+    wide = torch.full((len(c["points"]), 9), 3.0, device=dev)
+    wide[:, 0:8:2] = torch.from_numpy(c["points"]).to(dev)
+    view = wide[:, ::2][:, :4]
+    assert view.stride(1) == 2 and view.shape == (len(c["points"]), 4)
     got = to_host(ops.point_targets(view, gt, ext, 3, mean_size=mean, want_box=True, want_part=True))
     assert not seq.mismatches(got, cases.run(c))
 

@@ -2,8 +2,10 @@
 tools/make_golden_point_targets.py recorded from the reference's own PointHeadTemplate.assign_stack_targets and
 PointResidualCoder -- labels and box labels bit for bit, part labels within the bound DESIGN.md section 7l derives from
 the inputs -- and the fixture holds every case it promises.  Also: every case of tests/point_targets_cases.py holds its
-edge, the branch that is not provided, the reference's assertions, the opt-in binding, the header / ctypes mirror of the
-new entry point, no scratch and no spill in the kernel, and the benchmark's yardstick against the recorded outputs."""
+edge (the cases of PAST, past 65 boxes, 3 samples and one workgroup's rounds, too), a second restatement that walks
+as the kernel does (workgroups, rounds, tiles) equals the first everywhere and every fault it can be asked for shows on a
+named PAST case, the branch that is not provided, the reference's assertions, the opt-in binding, the header / ctypes
+mirror of the new entry point, no scratch and no spill in the kernel, and the benchmark's yardstick against the recorded outputs."""
 import importlib.util
 import json
 import os
@@ -18,6 +20,7 @@ import point_targets_seq as seq
 import roipool_seq
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "point_targets.npz")
+GOLD_CROWD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "point_targets_crowd.npz")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
@@ -25,6 +28,11 @@ F = np.float32
 @pytest.fixture(scope="module")
 def gold():
     return dict(np.load(GOLD))
+
+
+@pytest.fixture(scope="module")
+def crowd():
+    return dict(np.load(GOLD_CROWD))
 
 
 def ours_of(gold, name):
@@ -38,12 +46,26 @@ def test_fixture_is_small(gold):
     assert all(150 <= len(gold[n + "_points"]) <= 400 for n in seq.scenes(gold))
 
 
-def test_restatement_reproduces_the_reference(gold):
-    for name in seq.scenes(gold):
-        cfg, pts, gt, ext, _ = seq.scene_inputs(gold, name)
-        ref = seq.recorded(gold, name)
+def test_crowd_fixture_is_small(crowd):
+    assert os.path.getsize(GOLD_CROWD) <= 96 * 1024
+    assert seq.scenes(crowd) == ["crowd"]
+    cfg, pts, gt, _, mean = seq.scene_inputs(crowd, "crowd")
+    assert gt.shape == (3, 140, 8) and [int(gt[b].any(axis=1).sum()) for b in range(3)] == [140, 100, 66]
+    assert 380 <= len(pts) <= 420 and cfg["want_box"] and cfg["want_part"] and cfg["num_class"] == 3 and mean.shape == (3, 3)
+    k = seq.sample_of(pts, 3)
+    assert min(len(set(k[i:i + 64])) for i in range(0, len(k) - 63, 64)) >= 3      # shuffled
+
+
+def every_scene(*recs):
+    return [(rec, name) for rec in recs for name in seq.scenes(rec)]
+
+
+def test_restatement_reproduces_the_reference(gold, crowd):
+    for rec, name in every_scene(gold, crowd):
+        cfg, pts, gt, ext, _ = seq.scene_inputs(rec, name)
+        ref = seq.recorded(rec, name)
         bound = seq.part_bound(pts, gt, ext, cfg["want_box"]) if cfg["want_part"] else None
-        why = seq.mismatches(ours_of(gold, name), ref, bound=bound)
+        why = seq.mismatches(ours_of(rec, name), ref, bound=bound)
         assert not why, name + "\n" + "\n".join(why)
         assert ref["point_cls_labels"].dtype == np.int64 and (ref["point_cls_labels"] > 0).any()
         assert seq.same_bits(ext, seq.enlarge(gt, cfg["extra_width"]))
@@ -90,9 +112,11 @@ def test_the_coder_clamp_reaches_the_part_labels(gold):
     assert len(at) == 2 and not np.isfinite(ref[:, 0]).any()
 
 
-def test_fixture_cases(gold):
+def test_fixture_cases(gold, crowd):
     got = seq.fixture_cases(gold)
     assert len(got) >= 15 and all(got.values()), [k for k, v in got.items() if not v]
+    got = seq.crowd_cases(crowd, cases.TILE)
+    assert len(got) >= 4 and all(got.values()), [k for k, v in got.items() if not v]
 
 
 @pytest.mark.parametrize("name", list(cases.CASES))
@@ -107,6 +131,103 @@ def test_kernel_constants_are_the_ones_the_cases_cross():
     assert (cases.WG, cases.TILE) == (256, 64)
     assert {"N = 255", "N = 256", "N = 257", "N = 1", "N = 63", "N = 65"} <= set(cases.CASES)
     assert cases.CASES["last row past the tile"]()["gt"].shape[1] == cases.TILE + 1
+    # PAST crosses 2 * TILE and 3 * TILE rows, 16 and 40 rounds in one workgroup, and a workgroup of one point
+    rows = {n: cases.past(n)["gt"].shape[1] for n in cases.PAST}
+    assert any(m == 2 * cases.TILE for m in rows.values()) and any(m == 2 * cases.TILE + 1 for m in rows.values())
+    assert any(2 * cases.TILE < m < 3 * cases.TILE for m in rows.values()) and any(m > 3 * cases.TILE for m in rows.values())
+    assert max(rounds_per_workgroup(cases.past("16 samples in one workgroup"))) == 16
+    assert max(rounds_per_workgroup(cases.past("40 samples shuffled, two tiles"))) == 40
+    assert 4 * cases.WG + 1 in {len(cases.past(n)["points"]) for n in cases.PAST}
+
+
+def rounds_per_workgroup(c):
+    k = seq.sample_of(c["points"], c["gt"].shape[0])
+    return [len(set(k[i:i + cases.WG]) - {-1}) for i in range(0, len(k), cases.WG)]
+
+
+@pytest.mark.parametrize("name", list(cases.PAST))
+def test_every_case_past_the_tile_holds_its_edge(name):
+    c = cases.past(name)
+    assert c["present"](c)
+    assert c["gt"].shape[0] <= 40 and c["gt"].shape[1] <= 4 * cases.TILE and len(c["points"]) <= 20100
+    assert c["ext"].shape == c["gt"].shape and c["points"].dtype == F
+    assert c["num_class"] == 3 and c["mean"] is cases.KITTI and c["want_box"] and c["want_part"]
+
+
+# ------------------------------------------------------------------------------------------------ the kernel's walk
+def tiled(c, fault=None):
+    return seq.membership_tiled(c["points"], c["gt"], c["ext"], cases.WG, cases.TILE, fault)
+
+
+def same_membership(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", list(cases.CASES) + list(cases.PAST))
+def test_the_tiled_walk_is_the_restatement(name):
+    c = cases.past(name) if name in cases.PAST else cases.CASES[name]()
+    assert same_membership(tiled(c), seq.membership(c["points"], c["gt"], c["ext"]))
+
+
+def test_the_tiled_walk_is_the_restatement_on_the_fixtures(gold, crowd):
+    for rec, name in every_scene(gold, crowd):
+        _, pts, gt, ext, _ = seq.scene_inputs(rec, name)
+        for wg, tile in ((cases.WG, cases.TILE), (64, 8)):
+            assert same_membership(seq.membership_tiled(pts, gt, ext, wg, tile), seq.membership(pts, gt, ext)), name
+
+
+# fault -> the PAST cases on which it changes idx, the enlarged hit or a label (each is asserted)
+SEEN_BY = {
+    "tile index restarts": ["M = 2 tiles + 1", "M = 3 tiles + 37", "first hit wins across tiles", "enlarged rows elsewhere",
+                            "detector-sized"],
+    "last tile wins": ["M = 2 tiles", "M = 3 tiles + 37", "first hit wins across tiles", "enlarged rows elsewhere"],
+    "enlarged latch per tile": ["M = 2 tiles", "enlarged rows elsewhere", "40 samples shuffled, two tiles",
+                                "one point in the tail workgroup"],
+    "three rounds only": ["16 samples in one workgroup", "40 samples shuffled, two tiles"],
+    "rounds in order of appearance": ["40 samples shuffled, two tiles", "samples descending"],
+    "sample by rank among those present": ["samples that no point names"],
+    "minimum of the first wavefront only": ["16 samples in one workgroup", "samples descending", "detector-sized"],
+    "strays join sample 0": ["a wavefront and a workgroup of strays"],
+}
+
+
+def test_every_fault_is_named_with_its_cases():
+    assert set(SEEN_BY) == set(seq.FAULTS) and all(set(v) <= set(cases.PAST) for v in SEEN_BY.values())
+    assert set().union(*SEEN_BY.values()) == set(cases.PAST)               # and every PAST case sees a fault
+
+
+@pytest.mark.parametrize("fault", list(seq.FAULTS))
+def test_every_fault_shows_on_its_cases(fault):
+    for name in SEEN_BY[fault]:
+        c = cases.past(name)
+        m = tiled(c, fault)
+        out = seq.assign(c["points"], c["gt"], c["ext"], c["num_class"], c["mean"], c["want_box"], c["want_part"], member=m)
+        true = seq.membership(c["points"], c["gt"], c["ext"])
+        assert not np.array_equal(m[1], true[1]) or not np.array_equal(out["point_cls_labels"], c["want"]["point_cls_labels"]), \
+            (fault, name)
+        assert seq.mismatches(out, c["want"]), (fault, name)               # what the device tests compare
+
+
+def test_the_crowd_scene_sees_the_faults_of_the_tile_loop(crowd):
+    """against what the reference itself recorded, not against the restatement"""
+    cfg, pts, gt, ext, mean = seq.scene_inputs(crowd, "crowd")
+    ref = seq.recorded(crowd, "crowd")
+    bound = seq.part_bound(pts, gt, ext, cfg["want_box"])
+    for fault in (None, "tile index restarts", "last tile wins", "enlarged latch per tile"):
+        m = seq.membership_tiled(pts, gt, ext, cases.WG, cases.TILE, fault)
+        out = seq.assign(pts, gt, ext, cfg["num_class"], mean, cfg["want_box"], cfg["want_part"], member=m)
+        assert bool(seq.mismatches(out, ref, bound=bound)) == (fault is not None), fault
+
+
+def test_the_old_cases_miss_all_faults_of_the_walk_but_three():
+    """why PAST exists: of the eight faults, the 29 cases of CASES see the order of the rounds ("shuffled bs_idx"), the
+    missing reduction across wavefronts and the strays; the tile loop's three and the other two of the round loop pass"""
+    seen = {f: [n for n, mk in cases.CASES.items() for c in [mk()] if not same_membership(tiled(c, f), tiled(c))]
+            for f in seq.FAULTS}
+    assert seen["rounds in order of appearance"] == ["shuffled bs_idx"] and seen["strays join sample 0"] == ["bs_idx -1, B, 0.5"]
+    assert seen["minimum of the first wavefront only"]
+    assert not any(seen[f] for f in ("tile index restarts", "last tile wins", "enlarged latch per tile", "three rounds only",
+                                     "sample by rank among those present"))
 
 
 # ------------------------------------------------------------------------------------------------ the Python side
@@ -239,7 +360,7 @@ def test_header_ctypes_mirror_and_no_scratch():
 
 
 # ------------------------------------------------------------------------------------------------ the benchmark's yardstick
-def test_the_benchmark_yardstick_computes_the_reference_results(gold):
+def test_the_benchmark_yardstick_computes_the_reference_results(gold, crowd):
     """tools/point_targets_bench.py's PyTorch restatement of the path before this op, on the CPU with the numpy
     membership in place of the device's points_in_boxes_gpu, against the recorded outputs"""
     import torch
@@ -249,10 +370,10 @@ def test_the_benchmark_yardstick_computes_the_reference_results(gold):
 
     def pib(points, boxes):
         return torch.from_numpy(roipool_seq.points_in_boxes(boxes.numpy(), points.numpy()))
-    for name in seq.scenes(gold):
-        cfg, pts, gt, ext, mean = seq.scene_inputs(gold, name)
+    for rec, name in every_scene(gold, crowd):
+        cfg, pts, gt, ext, mean = seq.scene_inputs(rec, name)
         out = bench.yard_assign(torch.from_numpy(pts.copy()), torch.from_numpy(gt.copy()), torch.from_numpy(ext.copy()),
                                 cfg["num_class"], None if mean is None else torch.from_numpy(mean.copy()), cfg["want_box"],
                                 cfg["want_part"], pib)
         out = {k: None if v is None else v.numpy() for k, v in out.items()}
-        assert not seq.mismatches(out, seq.recorded(gold, name)), name
+        assert not seq.mismatches(out, seq.recorded(rec, name)), name

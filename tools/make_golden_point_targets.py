@@ -16,7 +16,13 @@ part, box, box without mean size, part, labels only), a few hundred points each.
     and every part label within the bound of DESIGN.md section 7l, computed from the inputs;
   * every case of point_targets_seq.fixture_cases, and the fixture's size.
 
-Usage:  python tools/make_golden_point_targets.py        (writes tests/golden/point_targets.npz)
+A sixth scene, ``crowd``, goes into a file of its own, tests/golden/point_targets_crowd.npz (the first file keeps its
+five scenes and its bytes): B = 3, M = 140 rows of which 140 / 100 / 66 are live, 400 shuffled points, box and part
+labels, three classes, mean sizes -- past two tiles of the kernel's 64 rows, under the same conditions, and with the
+cases of point_targets_seq.crowd_cases.  It is drawn from a random state of its own after the five, so they stay as
+they were.  A fixture whose arrays are all unchanged is left alone on disk (a zip archive carries the time of writing).
+
+Usage:  python tools/make_golden_point_targets.py        (writes both files)
 """
 import json
 import os
@@ -160,6 +166,61 @@ def make_scene(rs, cfg, B, M, n_live, n_points):
     return np.ascontiguousarray(pts[order]), gt
 
 
+def make_crowd(rs, cfg, n_points=400, M=140, n_live=(140, 100, 66)):
+    """-> points (n_points, 4) shuffled, gt (3, M, 8): the live boxes one per cell of a 12 m grid (none touches another),
+    but for one row of the third tile (sample 0) and one of the second (sample 1) that enclose a row of the first; points
+    in and around rows of every tile, points 5 cm outside rows of the last tile, the origin (zero rows only), strays"""
+    mean = np.asarray(cfg["mean_size"], dtype=F).reshape(-1, 3)
+    B = len(n_live)
+    gt = np.zeros((B, M, 8), dtype=F)
+    around = {0: (131, 10), 1: (70, 3)}       # sample: (the enclosing row, the row it encloses)
+    for b in range(B):
+        for j in range(n_live[b]):
+            c = 1 + j % 3
+            against = [[mean[c - 1, d]] for d in range(3)]
+            if j == around.get(b, (None,))[0]:
+                gt[b, j] = gt[b, around[b][1]]
+                gt[b, j, 3:6] = [size(rs, 4.6, 5.2, against[0]), size(rs, 2.1, 2.6, against[1]), size(rs, 1.9, 2.2, against[2])]
+                gt[b, j, 7] = c
+                continue
+            ctr = [-66 + 12 * (j % 12) + rs.uniform(-2, 2), -66 + 12 * (j // 12) + rs.uniform(-2, 2), rs.uniform(-1.5, 0.5)]
+            gt[b, j] = [*ctr, size(rs, 3.0, 4.5, against[0]), size(rs, 1.4, 2.0, against[1]), size(rs, 1.3, 1.8, against[2]),
+                        heading(rs), c]
+
+    def at(b, j, u):
+        g = gt[b, j]
+        c, s = np.cos(g[6]), np.sin(g[6])
+        x, y, z = u[0] * g[3], u[1] * g[4], u[2] * g[5]
+        return [b, g[0] + x * c - y * s, g[1] + x * s + y * c, g[2] + z]
+
+    pts = []
+    rows = {0: sorted(set(range(0, 128, 5)) | set(range(128, 140))), 1: sorted(set(range(0, 100, 8)) | {3, 63, 64, 70, 99}),
+            2: sorted(set(range(0, 66, 6)) | {63, 64, 65})}
+    for b in range(B):
+        for j in rows[b]:
+            u = rs.uniform(-0.62, 0.62, (4, 3))           # beyond +-0.5: in the enlarged box only, or outside both
+            u[:2] *= 0.5
+            pts += [at(b, j, v) for v in u]
+    for j in range(133, 139):                             # 5 cm outside a row of the last tile: that enlarged row alone holds it
+        for sign in (-1, 1):
+            pts.append(at(0, j, [sign * (0.5 + 0.05 / gt[0, j, 3]), rs.uniform(-0.4, 0.4), rs.uniform(-0.4, 0.4)]))
+    pts += [[1, 0.0, 0.0, 0.0], [2, 0.0, 0.0, 0.0]]       # the origin: inside the zero rows of samples 1 and 2 alone
+    pts += [[B, 1.0, 1.0, 0.0], [-1, 1.0, 1.0, 0.0], [0.5, *gt[0, 0, :3]], [np.nan, *gt[0, 0, :3]]]
+    assert len(pts) <= n_points, len(pts)
+    while len(pts) < n_points:
+        pts.append([rs.randint(B), rs.uniform(-75, 75), rs.uniform(-75, 75), rs.uniform(-3, 1)])
+    pts = np.array(pts, dtype=F)
+    return np.ascontiguousarray(pts[rs.permutation(len(pts))]), gt
+
+
+def build_crowd():
+    rs = np.random.RandomState(20261020)
+    kitti = [[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]]
+    cfg = dict(extra_width=EXTRA, num_class=3, use_mean_size=True, mean_size=kitti, want_box=True, want_part=True)
+    pts, gt = make_crowd(rs, cfg)
+    return {"crowd": (cfg, pts, gt, np.asarray(kitti, dtype=F))}
+
+
 def build_scenes():
     rs = np.random.RandomState(20261019)
     kitti = [[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]]
@@ -182,10 +243,10 @@ def build_scenes():
     return out
 
 
-def main():
+def record(job):
+    """run the reference on the scenes of `job` and check the restatement against it -> the arrays to save"""
     import torch
     import point_targets_seq as seq
-    job = build_scenes()
     print("drawn by rejection: %(candidates)d candidates, %(dropped)d dropped" % DRAWS)
     assert DRAWS["dropped"] * 4 <= DRAWS["candidates"], DRAWS
     with tempfile.TemporaryDirectory() as work:
@@ -229,14 +290,32 @@ def main():
             rec[name + "_part"] = ref["point_part_labels"]
         lab = ref["point_cls_labels"]
         print(name, "points", pts.shape, "gt", gt.shape, "foreground", int((idx >= 0).sum()), "ignored", int((lab == -1).sum()))
-    path = os.path.join(GOLD, "point_targets.npz")
-    np.savez_compressed(path, **rec)
-    cases = seq.fixture_cases(dict(np.load(path)))
+    return rec
+
+
+def save(path, rec, cases_of, limit):
+    """write `rec` unless the file holds exactly these arrays already; then check its cases and its size"""
+    import point_targets_seq as seq
+    have = dict(np.load(path)) if os.path.exists(path) else {}
+    if sorted(have) == sorted(rec) and all(have[k].dtype == np.asarray(v).dtype and have[k].shape == np.asarray(v).shape
+                                           and have[k].tobytes() == np.asarray(v).tobytes() for k, v in rec.items()):
+        print(path, "holds these arrays already: left as it is")
+    else:
+        np.savez_compressed(path, **rec)
+    cases = cases_of(dict(np.load(path)))
     missing = [k for k, v in cases.items() if not v]
     assert not missing, f"the fixture lacks: {missing}"
     size_ = os.path.getsize(path)
-    assert size_ <= 64 * 1024, size_
+    assert size_ <= limit, size_
     print(path, size_, "bytes;", len(cases), "cases")
+
+
+def main():
+    import point_targets_cases
+    import point_targets_seq as seq
+    save(os.path.join(GOLD, "point_targets.npz"), record(build_scenes()), seq.fixture_cases, 64 * 1024)
+    save(os.path.join(GOLD, "point_targets_crowd.npz"), record(build_crowd()),
+         lambda rec: seq.crowd_cases(rec, point_targets_cases.TILE), 96 * 1024)
 
 
 if __name__ == "__main__":
