@@ -5,7 +5,8 @@ A case is a dict: name, indices (N, 4) int32 [b, z, y, x], batch_size, shape [D,
 cin, cout, bias (bool), seed, dense (small enough to densify), and `present`: a function of the case that asserts FROM
 THE INPUTS that the edge the case is named after is there.  The smallest shapes at which the kernels can still go wrong:
 a convolution workgroup owns 64 output rows, the sort works in tiles of 2048 keys and sub-blocks of 64, the scans in
-blocks of 1024, the weight gradient in segments of 1024 rows and chunks of 32.
+blocks of 1024, the weight gradient in segments of 1024 rows and chunks of 32 -- and, past 32 768 rows, in 32 longer
+segments, which only that many rows can reach (the segments family).
 """
 import functools
 
@@ -183,8 +184,102 @@ def huge():
             for i, geo in enumerate(("subm", "s2p1"))]
 
 
+def passes(sentinel):
+    """8-bit passes of the radix sort over the bits of a sentinel key (sort64_bit_length, 8 bits per pass)"""
+    return -(-int(sentinel).bit_length() // 8)
+
+
+def huge_many():
+    """the shape of huge() with 3 001 sites: keys past 32 bits in sorts that cross tiles (2 048 keys) and sub-blocks (64).
+    A 5-pass sort with the payload is the input sort of every case; a 5-pass keys-only sort is the candidate sort of a
+    strided case whose OUTPUT grid has more than 2^32 cells, which at stride 2 takes B = 8."""
+    D, H, W = shape = [1000, 2000, 2200]
+
+    def sites(seed, batch_size):
+        """3 001 unique sites drawn coordinate by coordinate (a choice over the 8.8e9 cells would permute them all): 26
+        clusters of 12 in a 3 x 3 x 3 neighbourhood, one of them past key 2^32 in cloud 0, the rest uniform"""
+        rng = np.random.default_rng(seed)
+        centres = np.stack([rng.integers(0, batch_size, 26), rng.integers(1, D - 1, 26), rng.integers(1, H - 1, 26),
+                            rng.integers(1, W - 1, 26)], axis=1)
+        centres[0] = (0, D - 3, H // 2, W // 2)
+        centres[1] = (batch_size - 1, D - 5, H // 3, W // 3)
+        planted = centres[:, None, :].repeat(12, axis=1)
+        planted[:, :, 1:] += rng.integers(-1, 2, (26, 12, 3))
+        planted = planted.reshape(-1, 4)
+        rows = np.concatenate([planted, np.stack([rng.integers(0, batch_size, 4000), rng.integers(0, D, 4000),
+                                                  rng.integers(0, H, 4000), rng.integers(0, W, 4000)], axis=1)])
+        _, first = np.unique(rows, axis=0, return_index=True)
+        rows = rows[np.sort(first)][:3001]
+        return rows[rng.permutation(len(rows))].astype(np.int32)
+
+    def present(c):
+        D, H, W = c["shape"]
+        B, n, K = c["batch_size"], len(c["indices"]), int(np.prod(seq.triple(c["kernel"])))
+        assert n == 3001 and n > 2048 and n * K > 2048 * 8 and len(site_set(c)) == n
+        key = ((c["indices"][:, 0].astype(np.int64) * D + c["indices"][:, 1]) * H + c["indices"][:, 2]) * W + c["indices"][:, 3]
+        for b in (0, B - 1):   # keys above 2^32 in the first and in the last cloud
+            assert (key[c["indices"][:, 0] == b] > 2 ** 32).any()
+        # the input sentinel B D H W: 8.8e9 at B = 2 is 34 bits, 3.52e10 at B = 8 is 36 bits; ceil(34 / 8) = ceil(36 / 8) = 5
+        cells_in = B * D * H * W
+        assert cells_in.bit_length() == {2: 34, 8: 36}[B] and passes(cells_in) == 5
+        out_idx, oshape, nbr, nbr_t = expected(c["name"])
+        cells_out = B * int(np.prod(oshape))
+        if c["subm"]:
+            assert cells_out == cells_in
+        elif B == 2:
+            # the output sentinel 2 * 500 * 1000 * 1100 = 1.1e9 is 31 bits: the keys-only sort of this case has 4 passes
+            assert oshape == [500, 1000, 1100] and cells_out.bit_length() == 31 and passes(cells_out) == 4
+        else:
+            # 8 * 500 * 1000 * 1100 = 4.4e9 is 33 bits, ceil(33 / 8) = 5: a 5-pass keys-only sort of n K = 81 027 keys
+            assert oshape == [500, 1000, 1100] and cells_out.bit_length() == 33 and passes(cells_out) == 5
+            okey = ((out_idx[:, 0].astype(np.int64) * oshape[0] + out_idx[:, 1]) * oshape[1] + out_idx[:, 2]) * oshape[2] + out_idx[:, 3]
+            assert (okey > 2 ** 32).any() and len(out_idx) > 2048
+        # the clusters make the maps more than the centre (submanifold) or one input per output (strided)
+        assert ((nbr >= 0).sum(0) > 1).sum() > 100
+    return [case("huge_many_subm", sites(80, 2), 2, shape, "subm", present, seed=80, dense=False),
+            case("huge_many_s2p1", sites(81, 2), 2, shape, "s2p1", present, seed=81, dense=False, bias=False),
+            case("huge_many_b8_s2p1", sites(82, 8), 8, shape, "s2p1", present, seed=82, dense=False, cin=3, cout=5)]
+
+
+def segments():
+    """row counts around the weight gradient's segmentation (seq.wgrad_segments): one full segment, the first seam, a
+    seg_rows that is no multiple of the 32-row chunk, exactly at the cap of 32 segments and past it, where seg_rows
+    exceeds 1024"""
+    small, big = [11, 30, 34], [21, 120, 128]
+
+    def has(n_out, segs, seg_rows, at_least=False):
+        def present(c):
+            out_idx, oshape, nbr, nbr_t = expected(c["name"])
+            n = len(out_idx)
+            assert n > n_out if at_least else n == n_out
+            assert not c["subm"] or n == len(c["indices"])
+            s, rows = seq.wgrad_segments(n)
+            assert s == segs and (at_least or rows == seg_rows)
+            assert s == max(1, min(32, -(-n // 1024))) and rows == -(-n // s) and (s - 1) * rows < n <= s * rows
+            if n > 32768:
+                assert rows > 1024 and -(-n // 1024) > 32   # the cap binds: the 1024-row rule alone would cut more segments
+            if s > 1:   # the first and the last row of every segment contribute at some offset
+                for q in range(s):
+                    for o in (q * rows, min((q + 1) * rows, n) - 1):
+                        assert (nbr[:, o] >= 0).any(), (c["name"], q, o)
+                # ... and some seam has rows on both of its sides that contribute at the same offset
+                seams = np.arange(1, s) * rows
+                assert ((nbr[:, seams - 1] >= 0) & (nbr[:, seams] >= 0)).any()
+        return present
+    out = []
+    for i, (n, segs, rows, shape, cin, cout, bias) in enumerate(((1024, 1, 1024, small, 4, 16, True), (1025, 2, 513, small, 3, 5, False),
+                                                                 (2048, 2, 1024, small, 4, 5, True), (32768, 32, 1024, big, 3, 16, False),
+                                                                 (32769, 32, 1025, big, 4, 16, True), (33797, 32, 1057, big, 3, 5, True))):
+        out.append(case(f"seg{n}_subm", random_sites(90 + i, n, 1, shape), 1, shape, "subm", has(n, segs, rows), cin=cin, cout=cout,
+                        bias=bias, seed=90 + i, dense=False))
+    assert -(-33797 // 1024) == 34 and 32769 - 31 * 1025 == 994
+    out.append(case("seg_many_s2p1", random_sites(97, 30000, 1, big), 1, big, "s2p1", has(32768, 32, None, at_least=True), cin=4, cout=5,
+                    bias=False, seed=97, dense=False))
+    return out
+
+
 def channels():
-    pairs = [(1, 4), (3, 16), (4, 16), (5, 32), (16, 3), (32, 64), (64, 128), (128, 5), (128, 128), (16, 16), (64, 64), (33, 65)]
+    pairs =[(1, 4), (3, 16), (4, 16), (5, 32), (16, 3), (32, 64), (64, 128), (128, 5), (128, 128), (16, 16), (64, 64), (33, 65)]
     out = []
     for i, (cin, cout) in enumerate(pairs):
         geo = "s2p1" if i % 3 == 1 else "subm"
@@ -215,7 +310,7 @@ def values():
 @functools.lru_cache(maxsize=None)
 def all_cases():
     out = []
-    for fam in (sizes, batches, borders, occupancy, backbone_layers, huge, channels, values):
+    for fam in (sizes, batches, borders, occupancy, backbone_layers, huge, channels, values, huge_many, segments):
         out.extend(fam())
     assert len({c["name"] for c in out}) == len(out)
     return tuple(out)
@@ -239,3 +334,10 @@ def expected_values(name):
     x, w, b, dy = tensors(c)
     _, _, nbr, nbr_t = expected(name)
     return seq.forward32(x, w, b, nbr), seq.input_grad32(dy, w, nbr_t)
+
+
+@functools.lru_cache(maxsize=None)
+def expected_grads(name):
+    """(weight_grad32, bias_grad32) of the restatement on tensors(case), computed once and shared"""
+    x, w, b, dy = tensors(get(name))
+    return seq.weight_grad32(x, dy, expected(name)[2]), seq.bias_grad32(dy)

@@ -68,6 +68,8 @@ def sizes():
             assert len(c["indices"]) == n and (n % 64 or n in (0, 64))
             if n > 3000:
                 assert n > 2048 and (class_counts(c) > 128).all()   # two sort tiles, several tiles in every class
+                coarse = len(expected(c["name"])[0])   # the weight gradient walks the coarse rows: a seam, off the 32-row chunks
+                assert coarse > 1024 and seq.wgrad_segments(coarse)[0] == 2 and seq.wgrad_segments(coarse)[1] % 32
         out.append(case(f"n{n}", sc.random_sites(10 + n, n, 1, [11, 30, 34]), 1, [11, 30, 34], "s2p1", present, seed=n))
     return out
 
@@ -171,3 +173,17 @@ def expected_values(name):
     x, w, b, dy = tensors(c)
     coarse, _, table, _, _ = expected(name)
     return inv.forward32(x, w, b, table), inv.input_grad32(dy, w, table, len(coarse))
+
+
+@functools.lru_cache(maxsize=None)
+def expected_weight_grad(name):
+    """The weight gradient in the order the device adds in: the sums of spconv_seq.weight_grad32 over the COARSE rows --
+    segments of them in ascending order, coarse row o reading fine row nbr[k, o], the inverse of the pairs table -- with
+    the two sides exchanged, (K, Cout, Cin), transposed.  -> dw (K, Cin, Cout) float32"""
+    x, w, b, dy = tensors(get(name))
+    coarse, _, table, _, _ = expected(name)
+    nbr = np.full((table.shape[0], len(coarse)), -1, dtype=np.int32)
+    k, fine = np.nonzero(table >= 0)
+    nbr[k, table[k, fine]] = fine
+    assert (nbr >= 0).sum() == (table >= 0).sum()   # a coarse row writes one fine site per offset
+    return np.ascontiguousarray(seq.weight_grad32(dy, x, nbr).transpose(0, 2, 1))

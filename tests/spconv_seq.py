@@ -3,7 +3,8 @@ imports nothing of modest_amd.
 
 Sites are a dict from (b, z, y, x) to the row.  Offset k = (kz_i * ky + ky_i) * kx + kx_i.  The float32 functions add in
 the stated order -- k ascending, absent neighbours skipped, channel ascending, product and sum rounded separately --
-vectorised over the rows and the output channels only, which the order does not concern.  The float64 functions return
+vectorised over the rows and the output channels only, which the order does not concern.  The weight and bias gradients
+add the rows of a segment in ascending order and then the segments (wgrad_segments).  The float64 functions return
 the same sums in float64 together with S = sum |a| |b| per element, for the bound gamma_n * S.
 """
 import itertools
@@ -113,6 +114,67 @@ def input_grad32(dy, w, nbr_t):
         for co in range(cout):
             acc[rows] = acc[rows] + (dy[src, co][:, None] * w[k, :, co][None, :])
     return acc
+
+
+WG_SEG_MAX, WG_SEG_ROWS = 32, 1024
+
+
+def wgrad_segments(n_out):
+    """-> (segments, seg_rows): the rows of a weight or bias gradient are cut into min(32, ceil(n_out / 1024)) segments
+    (at least one) of ceil(n_out / segments) rows; the last one may be shorter"""
+    n_out = int(n_out)
+    segments = max(1, min(WG_SEG_MAX, -(-n_out // WG_SEG_ROWS)))
+    return segments, -(-n_out // segments)
+
+
+def weight_grad32(x, dy, nbr):
+    """x (N_in, Cin), dy (N_out, Cout), nbr (K, N_out) -> dw (K, Cin, Cout) float32 in the contract's order: per (k, ci,
+    co) and segment an accumulator from +0.0f walks the segment's rows in ascending order, rows with nbr[k, o] < 0
+    skipped, acc = acc + (x[nbr[k, o], ci] * dy[o, co]) with the product and the sum rounded separately; then
+    dw = (((+0 + p_0) + p_1) + ...) over the segments in ascending order.
+
+    The device stages 32 rows at a time and adds 0 * 0 = +0 for an absent row of a staged chunk.  Skipping it here is
+    exact: an accumulator that starts at +0 can never become -0 (in round-to-nearest a sum is -0 only when both terms
+    are -0), so acc + (+0) leaves every bit of acc unchanged.
+
+    Vectorised over (segment, k, ci, co), which the order does not concern; the loop is over the position in the segment."""
+    x, dy, nbr = np.asarray(x, dtype=F), np.asarray(dy, dtype=F), np.asarray(nbr)
+    K, n_out = nbr.shape
+    cin, cout = x.shape[1], dy.shape[1]
+    segments, seg_rows = wgrad_segments(n_out)
+    part = np.zeros((segments, K, cin, cout), dtype=F)
+    starts = np.arange(segments, dtype=np.int64) * seg_rows
+    for j in range(seg_rows):
+        o = starts + j
+        oc = np.minimum(o, n_out - 1)
+        src = nbr[:, oc].T                                    # (segments, K)
+        live = (src >= 0) & (o < n_out)[:, None]
+        if not live.any():
+            continue
+        p = x[np.maximum(src, 0)][:, :, :, None] * dy[oc][:, None, None, :]
+        part = np.where(live[:, :, None, None], part + p, part)
+    dw = np.zeros((K, cin, cout), dtype=F)
+    for s in range(segments):
+        dw = dw + part[s]
+    return dw
+
+
+def bias_grad32(dy):
+    """dy (N_out, Cout) -> db (Cout,) float32: the segments of wgrad_segments, every row added in ascending order from
+    +0.0f, then the segments in ascending order from +0.0f"""
+    dy = np.asarray(dy, dtype=F)
+    n_out, cout = dy.shape
+    segments, seg_rows = wgrad_segments(n_out)
+    part = np.zeros((segments, cout), dtype=F)
+    starts = np.arange(segments, dtype=np.int64) * seg_rows
+    for j in range(seg_rows):
+        o = starts + j
+        live = o < n_out
+        part = np.where(live[:, None], part + dy[np.minimum(o, n_out - 1)], part)
+    db = np.zeros(cout, dtype=F)
+    for s in range(segments):
+        db = db + part[s]
+    return db
 
 
 def forward64(x, w, bias, nbr):

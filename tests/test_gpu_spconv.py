@@ -1,7 +1,8 @@
 """GPU: the sparse 3-D convolutions (modest_amd/csrc/spconv.hip through modest_amd.ops.spconv_* and the modules of
 modest_amd.utils.spconv) against the sequential restatement (tests/spconv_seq.py): the edge
 families of tests/spconv_cases.py, rulebook and forward and feature gradient bit for bit with no element excluded, into
-sentinel-filled outputs, twice; the weight and bias gradients inside gamma_n * S of the float64 sums; and the layer
+sentinel-filled outputs, twice; the weight and bias gradients inside gamma_n * S of the float64 sums and bit for bit in
+the stated order of segments and rows, up to and past the cap of 32 segments; and the layer
 sequence of VoxelBackBone8x against torch.nn.Conv3d in float64 on the CPU."""
 import os
 import sys
@@ -72,6 +73,10 @@ def test_device_is_the_restatement(name):
     assert (err <= seq.gamma(nw) * Sw).all(), (name, "dw", float((err - seq.gamma(nw) * Sw).max()))
     err = np.abs(first["db"].astype(np.float64) - db64)
     assert (err <= seq.gamma(nb) * Sb).all(), (name, "db", float((err - seq.gamma(nb) * Sb).max()))
+    # ... and bit for bit in the stated order of segments and rows, no element excluded
+    want_dw, want_db = sc.expected_grads(name)
+    assert seq.same_bits(first["dw"], want_dw), (name, "dw", int((first["dw"].view(np.int32) != want_dw.view(np.int32)).sum()))
+    assert seq.same_bits(first["db"], want_db), (name, "db", int((first["db"].view(np.int32) != want_db.view(np.int32)).sum()))
     # a second run gives identical bytes for every output
     again = run(c)
     for key in first:
@@ -175,6 +180,10 @@ def test_module_gradients_and_no_feature_gradient_when_not_needed():
     assert direct[0] is None and ops.SPCONV_CALLS["input_grad"] == before["input_grad"]
     gw = conv.weight.grad.clone()
     assert tuple(gw.shape) == tuple(conv.weight.shape) and torch.equal(gw, direct[1])
+    want_dw, want_db = sc.expected_grads(c["name"])
+    assert seq.same_bits(gw.cpu().numpy(), want_dw.reshape(tuple(conv.weight.shape)))   # the module's gradient is the restatement's
+    if c["bias"]:
+        assert seq.same_bits(conv.bias.grad.cpu().numpy(), want_db)
     # with a feature gradient: through dense(), which autograd differentiates
     conv.zero_grad()
     t = sparse_input(c, requires_grad=True)

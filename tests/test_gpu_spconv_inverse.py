@@ -2,8 +2,8 @@
 modest_amd.utils.spconv_inverse) against the sequential restatement (tests/spconv_inverse_seq.py):
 the edge families of tests/spconv_inverse_cases.py -- class order, forward on the class tiles and on the rows, feature
 gradient bit for bit with no element excluded, into sentinel-filled outputs, twice; weight and bias gradients inside
-gamma_n * S of the float64 sums --, what is launched and what is not, and an encoder-decoder chain of the layer kinds of
-UNetV2 against conv3d / conv_transpose3d in float64 on the CPU."""
+gamma_n * S of the float64 sums, the weight gradient also bit for bit in the stated order over the coarse rows --,
+what is launched and what is not, and an encoder-decoder chain of the layer kinds of UNetV2 against conv3d / conv_transpose3d in float64 on the CPU."""
 import os
 import sys
 
@@ -88,6 +88,9 @@ def test_device_is_the_restatement(name):
     assert (err <= seq.gamma(nw) * Sw).all(), (name, "dw", float((err - seq.gamma(nw) * Sw).max()))
     err = np.abs(first["db"].astype(np.float64) - db64)
     assert (err <= seq.gamma(nb) * Sb).all(), (name, "db", float((err - seq.gamma(nb) * Sb).max()))
+    # ... and the weight gradient bit for bit in the stated order over the coarse rows (the bias gradient is torch's sum)
+    want_dw = ic.expected_weight_grad(name)
+    assert seq.same_bits(first["dw"], want_dw), (name, "dw", int((first["dw"].view(np.int32) != want_dw.view(np.int32)).sum()))
     # a second run gives identical bytes for every output
     again = run(c)
     for key in first:

@@ -106,6 +106,105 @@ def test_restatement_rejects_bad_rows_and_the_huge_shape_is_cheap():
         assert not (nbr[:, rows[p]] == rows[q]).any() and not (nbr[:, rows[q]] == rows[p]).any()
 
 
+# ------------------------------------------------------------------------------------------------ weight and bias gradients
+def test_wgrad_segments():
+    want = {0: (1, 0), 1: (1, 1), 1024: (1, 1024), 1025: (2, 513), 32768: (32, 1024), 32769: (32, 1025), 100000: (32, 3125)}
+    for n, pair in want.items():
+        assert seq.wgrad_segments(n) == pair, n
+    for n in (1, 513, 1024, 1025, 2049, 31745, 32768, 32769, 33797, 100000):   # the segments cover the rows, none is empty
+        s, rows = seq.wgrad_segments(n)
+        assert (s - 1) * rows < n <= s * rows
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in sc.all_cases()])
+def test_gradient_restatement_inside_the_bound(name):
+    """weight_grad32 / bias_grad32 are sums of n - 1 terms in some order: inside gamma_n S of the float64 sums"""
+    c = sc.get(name)
+    x, w, b, dy = sc.tensors(c)
+    nbr = sc.expected(name)[2]
+    dw, db = sc.expected_grads(name)
+    (dw64, Sw, nw), (db64, Sb, nb) = seq.weight_grad64(x, dy, nbr)
+    assert dw.dtype == np.float32 and dw.shape == dw64.shape and db.dtype == np.float32 and db.shape == db64.shape
+    err = np.abs(dw.astype(np.float64) - dw64)
+    assert (err <= seq.gamma(nw) * Sw).all(), (name, "dw", float((err - seq.gamma(nw) * Sw).max()))
+    err = np.abs(db.astype(np.float64) - db64)
+    assert (err <= seq.gamma(nb) * Sb).all(), (name, "db", float((err - seq.gamma(nb) * Sb).max()))
+    if len(dy) > 64:
+        assert dw.any() and db.any()
+
+
+def scalar_gradients(x, dy, nbr):
+    """DESIGN.md section 7g's order of the weight and bias gradients as a literal loop over scalars, written apart from
+    tests/spconv_seq.py: nothing vectorised, every product and every sum one float32 operation"""
+    F = np.float32
+    K, n_out = len(nbr), len(dy)
+    cin, cout = x.shape[1], dy.shape[1]
+    segments = (n_out + 1023) // 1024
+    segments = 1 if segments < 1 else (32 if segments > 32 else segments)
+    seg_rows = (n_out + segments - 1) // segments
+    nbr = [list(map(int, row)) for row in nbr]
+    dw, db = np.empty((K, cin, cout), dtype=F), np.empty((cout,), dtype=F)
+    for k in range(K):
+        for ci in range(cin):
+            for co in range(cout):
+                total = F(0.0)
+                for s in range(segments):
+                    acc = F(0.0)
+                    for o in range(s * seg_rows, min((s + 1) * seg_rows, n_out)):
+                        i = nbr[k][o]
+                        if i < 0:
+                            continue
+                        product = F(x[i, ci] * dy[o, co])
+                        acc = F(acc + product)
+                    total = F(total + acc)
+                dw[k, ci, co] = total
+    for co in range(cout):
+        total = F(0.0)
+        for s in range(segments):
+            acc = F(0.0)
+            for o in range(s * seg_rows, min((s + 1) * seg_rows, n_out)):
+                acc = F(acc + dy[o, co])
+            total = F(total + acc)
+        db[co] = total
+    return dw, db
+
+
+def seam_inputs():
+    """3 offsets over 2 049 rows -- 3 segments of 683 rows, 683 = 21 * 32 + 11 --, half of the entries absent, the rows on
+    both sides of either seam present at offset 0, and -0.0 on either side"""
+    rng = np.random.default_rng(7)
+    n_in, n_out = 500, 2049
+    nbr = rng.integers(0, n_in, (3, n_out)).astype(np.int32)
+    nbr[rng.random((3, n_out)) < 0.5] = -1
+    nbr[0, [0, 682, 683, 1365, 1366, 2048]] = [5, 6, 7, 8, 9, 10]
+    nbr[2, :683] = -1   # an offset with a segment in which nothing contributes
+    x = rng.standard_normal((n_in, 2)).astype(np.float32)
+    dy = rng.standard_normal((n_out, 3)).astype(np.float32)
+    x[5], dy[683], dy[2048, 1] = np.float32(-0.0), np.float32(-0.0), np.float32(-0.0)
+    return x, dy, nbr
+
+
+@pytest.mark.parametrize("name", ["seg1025_subm", "seam2049", "signed_zeros_subm", "signed_zeros_s2p1"])
+def test_gradient_restatement_is_the_scalar_loop(name):
+    if name == "seam2049":
+        x, dy, nbr = seam_inputs()
+        assert seq.wgrad_segments(len(dy)) == (3, 683) and 683 % 32
+    else:
+        c = sc.get(name)
+        c["present"](c)
+        x, w, b, dy = sc.tensors(c)
+        nbr = sc.expected(name)[2]
+        if name == "seg1025_subm":
+            assert seq.wgrad_segments(len(dy)) == (2, 513) and 513 % 32
+        else:
+            assert np.signbit(x[x == 0]).any() and np.signbit(dy[0]).all()
+    want_dw, want_db = scalar_gradients(x, dy, nbr)
+    dw, db = seq.weight_grad32(x, dy, nbr), seq.bias_grad32(dy)
+    assert seq.same_bits(dw, want_dw), (name, int((dw.view(np.int32) != want_dw.view(np.int32)).sum()))
+    assert seq.same_bits(db, want_db), (name, int((db.view(np.int32) != want_db.view(np.int32)).sum()))
+    assert not np.signbit(dw[dw == 0]).any() and not np.signbit(db[db == 0]).any()   # a sum from +0 is never -0
+
+
 # ------------------------------------------------------------------------------------------------ the module API
 def test_shape_arithmetic():
     from modest_amd import ops

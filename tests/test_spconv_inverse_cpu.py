@@ -43,6 +43,13 @@ def test_restatement_is_the_forward_restatement_on_nbr_t(name):
     assert seq.same_bits(got, seq.forward32(x, w, b, nbr_t))
     # the feature gradient is the forward restatement with the transposed weights on nbr
     assert seq.same_bits(got_dx, seq.forward32(dy, np.ascontiguousarray(w.transpose(0, 2, 1)), None, nbr))
+    # the weight gradient in the device's order: spconv_seq's segmented sums over the coarse rows on the rulebook's nbr, the
+    # two sides exchanged, transposed; inside gamma_n S of the float64 sums
+    got_dw = ic.expected_weight_grad(name)
+    assert seq.same_bits(got_dw, np.ascontiguousarray(seq.weight_grad32(dy, x, nbr).transpose(0, 2, 1)))
+    (dw64, Sw, nw), _ = inv.weight_grad64(x, dy, table)
+    err = np.abs(got_dw.astype(np.float64) - dw64)
+    assert got_dw.shape == w.shape and (err <= seq.gamma(nw) * Sw).all(), (name, "dw", float((err - seq.gamma(nw) * Sw).max()))
     cls = inv.row_classes(c["indices"], c["stride"], c["padding"])
     for k_cls in np.unique(cls):
         used = np.nonzero((table[:, cls == k_cls] >= 0).any(1))[0].tolist()
