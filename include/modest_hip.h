@@ -1165,6 +1165,33 @@ int modest_point_targets(int64_t n, const float *points_dev, int64_t points_stri
                          int n_mean, int num_class, int64_t *cls_labels_dev, float *box_labels_dev,
                          float *part_labels_dev, void *stream);
 
+/* ---- a31 RoI proposal layer (RoIHeadTemplate.proposal_layer of OpenPCDet's two-stage detectors) ----------
+ * MULTI_CLASSES_NMS off.  The proposals of a whole batch in one call: enqueue only, no context, no device allocation, no
+ * synchronise, nothing read back, no (n, n / 64) suppression mask.  Every buffer [dev], contiguous.
+ *   box        (n_rows, box_cols = 7 + C) float32 [cx, cy, cz, dx, dy, dz, rz, ...]; NMS reads the first 7 columns;
+ *   cls        (n_rows, cls_cols = K >= 1) float32;
+ *   batch_index  NULL with kind 0 for the dense form, where row i belongs to sample i / rows_per_sample and
+ *              n_rows = batch_size * rows_per_sample; else (n_rows) of kind 1 float32, 2 int64 or 3 int32 (rows_per_sample
+ *              is not read): a row belongs to sample k iff its value equals k for a k in [0, batch_size), else to none.
+ *              A sample's rows need not be contiguous.
+ * Per sample: score = max over the class columns, label = its column (the LOWEST column among equal maxima; a NaN ranks
+ * above every number).  The min(pre_maxsize, rows of the sample) highest scores -- NaN first, equal scores in ascending
+ * row order, -0 == +0 -- are walked in that order by greedy NMS: a candidate is dropped iff its IoU with an earlier
+ * survivor, iou(survivor, candidate) of nms_bev (rotated != 0) or nms_normal (rotated == 0), is > thresh.  The first
+ * post_maxsize survivors go to rows 0.. of the outputs, every element of which is written:
+ *   rois        (batch_size, post_maxsize, box_cols) float32, the survivors' rows of box, then zeros;
+ *   roi_scores  (batch_size, post_maxsize) float32, then zeros;
+ *   roi_labels  (batch_size, post_maxsize) int64, label + 1, then ones.
+ * Limits (the call fails and launches nothing): post_maxsize <= 1024 (the kept list is held in LDS), batch_size <= 65535
+ * (16 sample bits of the sort key), n_rows <= 2^31 - 1, box_cols and cls_cols <= 4096.
+ * workspace 8-byte aligned, modest_proposals_workspace_bytes(n_rows) bytes, need not be initialised.                    */
+int64_t modest_proposals_workspace_bytes(int64_t n_rows);
+int modest_proposals(int64_t n_rows, int batch_size, int64_t rows_per_sample, const float *box_dev, int box_cols,
+                     const float *cls_dev, int cls_cols, const void *batch_index_dev, int batch_index_kind,
+                     int pre_maxsize, int post_maxsize, float thresh, int rotated, float *rois_dev,
+                     float *roi_scores_dev, int64_t *roi_labels_dev, void *workspace_dev, int64_t workspace_bytes,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,9 @@ SIGNATURES = {
                                                     VP, VP]),
     "modest_point_targets": (C.c_int, [C.c_int64, VP, C.c_int64, C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, VP,
                                        C.c_int64, C.c_int64, C.c_int64, VP, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "modest_proposals_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "modest_proposals": (C.c_int, [C.c_int64, C.c_int, C.c_int64, VP, C.c_int, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_int, VP, VP, VP, VP, C.c_int64, VP]),
 }
 
 _lib = None

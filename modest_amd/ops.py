@@ -1583,3 +1583,85 @@ def point_targets(points: torch.Tensor, gt_boxes: torch.Tensor, extend_gt_boxes:
                                        box.data_ptr() if box is not None else None,
                                        part.data_ptr() if part is not None else None, _stream()), "modest_point_targets")
     return labels, box, part
+
+
+# --------------------------------------------------------------------------- RoI proposal layer
+def proposals_workspace_bytes(n_rows: int) -> int:
+    nb = int(load().modest_proposals_workspace_bytes(int(n_rows)))
+    if nb < 0:
+        check(nb, "modest_proposals_workspace_bytes")
+    return nb
+
+
+_BATCH_INDEX_KINDS = {torch.float32: 1, torch.int64: 2, torch.int32: 3}
+
+
+def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int, pre_maxsize: int, post_maxsize: int,
+              thresh: float, rotated: bool = True, batch_index: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_proposals on PyTorch's current stream: enqueue only, nothing is read back.
+    Dense form: box_preds (B, N, 7 + C) and cls_preds (B, N, K) float32 with B == batch_size.  Stacked form: (N1 + N2 + ..,
+    7 + C) and (N1 + N2 + .., K) with batch_index (N1 + N2 + ..), a float or integer tensor of sample numbers in any order.
+    Per sample the min(pre_maxsize, rows) highest class maxima (NaN first, equal scores by ascending row, the lowest class
+    among equal maxima) are walked by greedy NMS at `thresh` (rotated: nms_gpu, else nms_normal_gpu) up to the
+    post_maxsize-th survivor.  -> rois (B, post_maxsize, 7 + C) float32, roi_scores (B, post_maxsize) float32, roi_labels
+    (B, post_maxsize) int64 (label + 1; 1 in the padding): freshly allocated, or the three tensors of `out` (of exactly
+    these shapes and types, contiguous, on the boxes' device), every element of which is written.  workspace: an uint8
+    tensor of at least proposals_workspace_bytes(rows) bytes, allocated when missing or too small."""
+    for t, name in ((box_preds, "box_preds"), (cls_preds, "cls_preds")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    dev = box_preds.device
+    if cls_preds.device != dev:
+        raise ValueError("box_preds and cls_preds are on different devices")
+    B = int(batch_size)
+    if batch_index is None:
+        if box_preds.ndim != 3 or cls_preds.ndim != 3 or box_preds.shape[:2] != cls_preds.shape[:2] or box_preds.shape[0] != B:
+            raise ValueError(f"dense form: box_preds {tuple(box_preds.shape)} and cls_preds {tuple(cls_preds.shape)} must be "
+                             f"(batch_size = {B}, N, 7 + C) and (batch_size, N, K)")
+        per, kind, bidx = int(box_preds.shape[1]), 0, None
+    else:
+        if box_preds.ndim != 2 or cls_preds.ndim != 2 or box_preds.shape[0] != cls_preds.shape[0] \
+                or not torch.is_tensor(batch_index) or batch_index.numel() != box_preds.shape[0]:
+            raise ValueError(f"stacked form: box_preds {tuple(box_preds.shape)}, cls_preds {tuple(cls_preds.shape)} and "
+                             f"batch_index must be (N, 7 + C), (N, K) and (N)")
+        if batch_index.device != dev:
+            raise ValueError("batch_index is on another device than box_preds")
+        bidx = batch_index.reshape(-1)
+        if bidx.dtype not in _BATCH_INDEX_KINDS:
+            bidx = bidx.float() if bidx.dtype.is_floating_point else bidx.long()
+        bidx = bidx.contiguous()
+        per, kind = 0, _BATCH_INDEX_KINDS[bidx.dtype]
+    cols, K = int(box_preds.shape[-1]), int(cls_preds.shape[-1])
+    if cols < 7 or K < 1:
+        raise ValueError(f"box_preds needs 7 + C columns and cls_preds K >= 1, got {cols} and {K}")
+    box, cls = box_preds.contiguous(), cls_preds.contiguous()
+    n = int(box.numel() // cols)
+    P = int(post_maxsize)
+    if P < 0 or B < 0 or int(pre_maxsize) < 0:
+        raise ValueError("batch_size, pre_maxsize and post_maxsize must not be negative")
+    want = (("rois", torch.float32, (B, P, cols)), ("roi_scores", torch.float32, (B, P)), ("roi_labels", torch.int64, (B, P)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
+    if len(out) != 3:
+        raise ValueError("out must be (rois, roi_scores, roi_labels)")
+    for t, (name, dtype, shape) in zip(out, want):
+        _dev(t, dtype, f"out {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.device != dev:
+            raise ValueError(f"out {name} is on {t.device}, box_preds on {dev}")
+    rois, scores, labels = out
+    lib = load()
+    nbytes = proposals_workspace_bytes(n)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    with torch.cuda.device(dev):
+        check(lib.modest_proposals(n, B, per, box.data_ptr(), cols, cls.data_ptr(), K,
+                                   bidx.data_ptr() if bidx is not None else None, kind, int(pre_maxsize), P, float(thresh),
+                                   int(bool(rotated)), rois.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                   workspace.data_ptr(), workspace.numel(), _stream()), "modest_proposals")
+    return rois, scores, labels

@@ -34,6 +34,11 @@ stand-in or of ``modest_amd.utils.spconv``; an installed or imported spconv is l
 of the point heads in one call -- on ``PointHeadTemplate`` of
 ``pcdet.models.dense_heads.point_head_template``, which is imported for it if it is not yet (after every other binding,
 so that the import finds the shims).  Where that module cannot be imported nothing is bound.
+
+``install(proposal_layer=True)`` sets ``modest_amd.utils.proposal_layer.proposal_layer`` -- the RoI proposal layer of the
+two-stage detectors in one call -- on ``RoIHeadTemplate`` of
+``pcdet.models.roi_heads.roi_head_template``, imported for it if it is not yet, after every other binding.  Where that
+module cannot be imported nothing is bound.
 """
 import importlib
 import importlib.util
@@ -61,6 +66,8 @@ ROIAWARE_NAME = "pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"
 ROIAWARE_POOL = "modest_amd.utils.roiaware_voxel_pool_cuda"   # bound to ROIAWARE_NAME by install(roiaware_pool=True)
 POINT_TARGETS_NAME = "pcdet.models.dense_heads.point_head_template"
 POINT_TARGETS = "modest_amd.utils.point_head_targets"   # its method set on PointHeadTemplate by install(point_targets=True)
+PROPOSAL_LAYER_NAME = "pcdet.models.roi_heads.roi_head_template"
+PROPOSAL_LAYER = "modest_amd.utils.proposal_layer"   # its method set on RoIHeadTemplate by install(proposal_layer=True)
 
 
 class StandIn(types.ModuleType):
@@ -152,8 +159,24 @@ def _bind_point_targets():
     return mod
 
 
+def _bind_proposal_layer():
+    """RoIHeadTemplate.proposal_layer := ours, in the reference's module if it is imported or can be
+    -> that module, or None"""
+    mod = sys.modules.get(PROPOSAL_LAYER_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(PROPOSAL_LAYER_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    head = getattr(mod, "RoIHeadTemplate", None)
+    if head is None:
+        return None
+    importlib.import_module(PROPOSAL_LAYER).bind(head)
+    return mod
+
+
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
-            sparse_inverse=False, point_targets=False):
+            sparse_inverse=False, point_targets=False, proposal_layer=False):
     """-> {name: module} of everything bound (also what an earlier call bound)"""
     bound = {}
     roiaware_before = sys.modules.get(ROIAWARE_NAME)
@@ -194,4 +217,8 @@ def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets
         mod = _bind_point_targets()
         if mod is not None:
             bound[POINT_TARGETS_NAME] = mod
+    if proposal_layer:
+        mod = _bind_proposal_layer()
+        if mod is not None:
+            bound[PROPOSAL_LAYER_NAME] = mod
     return bound
