@@ -3,6 +3,9 @@ clustered NMS proposals of tests/iou3d_cases.py (96 jittered copies of each of 4
 Each is the smallest shape at which the walk of csrc/proposals.hip can still go wrong; `present(case, stats)` asserts from
 the inputs and the restatement that the edge the case is named after is there.
 
+CASES are the shapes of the workloads; EDGE_CASES (below them) the inputs of a diverged or untrained detector and the
+kernel's limits themselves.
+
 A case is a dict: box, cls (numpy, stacked (n, .) or dense (B, N, .)), batch_index (None: dense), B, pre, post, thresh,
 rotated, present.  want(case) is the restatement's result, computed once per case and read-only.
 """
@@ -33,8 +36,9 @@ def stacked(box, cls, B=1, bidx=None, **kw):
     return c
 
 
-def stats_of(c):
-    """per sample: the chunked walk's statistics (proposals_seq.chunked_walk), its candidates and survivors"""
+def stats_of(c, rows_of=None):
+    """per sample: the chunked walk's statistics (proposals_seq.chunked_walk), its candidates and survivors; rows_of (a
+    list) receives each sample's surviving rows"""
     box, cls, n_per = seq._flat(c["box"], c["cls"], c["batch_index"])
     score, _ = seq.score_label(cls)
     smp = seq.sample_of(c["batch_index"], len(box), c["B"], n_per)
@@ -44,6 +48,8 @@ def stats_of(c):
         kept = seq.chunked_walk(box[cand], c["thresh"], c["rotated"], c["post"], stats=one) if len(cand) else []
         one.update(candidates=len(cand), kept=len(kept))
         per.append(one)
+        if rows_of is not None:
+            rows_of.append(cand[kept] if len(cand) else cand)
     return per
 
 
@@ -214,9 +220,225 @@ CASES = {
     "dense": dense(), "dense rows stacked": dense(True), "dense axis-aligned": dense(rotated=False),
     "past every capacity": past_every_capacity,
 }
+
+
+# ------------------------------------------------------------------------------------------------ the edges
+# A second registry, kept apart because the CPU test bounds CASES (rows, B, POST): scores as the detectors hand them over
+# (raw logits, mostly negative), boxes of a diverged detector, and every limit of csrc/proposals.hip run, not only refused.
+# Scores that must stay pairwise distinct are moved by exact maps only: the pool's lie on the 2^-24 grid of [0, 1), and
+# sc - 0.5 and sc - 1 are exact there.
+HALF = F(0.5)
+LOGIT = F(0.625)          # sc - 0.5 leaves 79 negative scores among the 512 kept of "logits", sc - 0.625 (as exact) 172
+PAYLOAD = 0x7FC12345      # a quiet NaN with a payload: extra box columns are copied, never computed with
+
+
+def logits(rotated=True):
+    def make():
+        p, sc = pool()
+        s = (sc - LOGIT)[:1000]
+
+        def present(c, st):
+            kept = want(c)[1][0, :st[0]["kept"]]
+            return (st[0]["kept"] == 512 and int((kept < 0).sum()) >= 100 and int((kept > 0).sum()) >= 100
+                    and len(np.unique(s)) == 1000 and is_distinct(c))
+        return stacked(p[:1000], s, post=512, thresh=0.85, rotated=rotated, present=present)
+    return make
+
+
+def logits_k3():
+    p, sc = pool()
+    three = np.stack([sc[:1000], sc[1000:2000], sc[2000:3000]], 1)
+    cls = three - F(0.875)      # mixed sign, the maximum negative on two rows in three
+    cls[::2] = three[::2] - F(1)      # every other row: all negative
+
+    def present(c, st):
+        k = st[0]["kept"]
+        _, scores, labels = want(c)
+        return ((c["cls"][::2] < 0).all() and (c["cls"][1::2] > 0).any() and (c["cls"][1::2] < 0).any()
+                and set(labels[0, :k]) == {1, 2, 3} and (scores[0, :k] < 0).any() and (scores[0, :k] > 0).any() and is_distinct(c))
+    return stacked(p[:1000], cls, post=512, thresh=0.85, present=present)
+
+
+EIGHT = np.array([1e-45, -1e-45, 0.0, -0.0, 1e-39, -1e-39, -0.0, 0.0], F)      # the scores of rows 0 .. 7
+EIGHT_ORDER = [4, 0, 2, 3, 6, 7, 1, 5]      # 1e-39, 1e-45, the four zeros by ascending row, -1e-45, -1e-39
+
+
+def zeros_and_denormals():
+    p, sc = pool()
+    s = (sc - HALF)[:300].copy()
+    s[:8] = EIGHT
+
+    def present(c, st):
+        rois, scores, _ = want(c)
+        at = [int(np.flatnonzero((rois[0] == c["box"][r]).all(1) & (scores[0].view(np.uint32) == EIGHT[r:r + 1].view(np.uint32)))[0])
+              for r in EIGHT_ORDER]
+        return (st[0]["kept"] == 300 and at == sorted(at) and (EIGHT[[0, 1, 4, 5]] != 0).all()
+                and (np.abs(EIGHT) < np.finfo(F).tiny).all() and len(np.unique(c["box"][:8], axis=0)) == 8)
+    return stacked(p[:300], s, post=300, thresh=np.inf, present=present)
+
+
+POISON = (np.nan, np.inf, -np.inf)
+ROTATED_COLUMNS = range(7)      # the columns poisoned in the rotated non-finite case
+
+
+def poisoned_rows():
+    """60 of the first 400 pool rows, each given NaN / +inf / -inf (cycled) in one of the columns 0 .. 6 (cycled), and
+    five degenerate ones: -> (rows, column or -1, boxes)"""
+    p, _ = pool()
+    box = p[:400].copy()
+    rows = np.sort(np.random.default_rng(1).choice(400, 65, replace=False))
+    col = np.full(65, -1)
+    for k, r in enumerate(rows[:60]):
+        col[k] = k % 7
+        box[r, col[k]] = POISON[k % 3]
+    a, b, c, d, e = rows[60:]
+    box[a, 3] = 0
+    box[b, 3:5] = 0
+    box[c, 3] = -1
+    box[d, 6] = 1e30
+    box[e, 0] = 3e38
+    return rows, col, box
+
+
+def non_finite(rotated=True, columns=range(7)):
+    def make():
+        _, sc = pool()
+        rows, col, box = poisoned_rows()
+        take = np.ones(400, bool)
+        take[rows[:60][~np.isin(col[:60], list(columns))]] = False      # a poisoned column that is left out: the row goes
+        extra = np.random.default_rng(2).random((400, 2)).astype(F)
+        extra[:, 0] = np.array([PAYLOAD], np.uint32).view(F)[0]
+        box, s, bad = np.concatenate([box, extra], 1)[take], sc[:400][take], np.isin(np.arange(400), rows)[take]
+
+        def present(c, st):
+            rois = want(c)[0][0, :st[0]["kept"]]
+            got = (c["box"][bad][:, None, :7].view(np.uint32) == rois[None, :, :7].view(np.uint32)).all(2).any(1)
+            clean = seq.survivors(c["box"][~bad], c["cls"][~bad], 1, c["pre"], c["post"], c["thresh"], c["rotated"],
+                                  c["batch_index"][~bad])[0]
+            return (not np.isfinite(c["box"][bad][:, :7]).all(1).all() and got.any() and not got.all()
+                    and len(clean) != st[0]["kept"] and (rois[:, 7].view(np.uint32) == PAYLOAD).all() and len(rois) > 100)
+        return stacked(box, s, post=400, thresh=0.7, rotated=rotated, present=present)
+    return make
+
+
+def post_full():
+    p, sc = pool()
+    return stacked(p, sc, post=seq.POST_MAX, thresh=0.9,
+                   present=lambda c, st: st[0]["kept"] == 1024 == seq.POST_MAX and st[0]["chunks"] >= 17 and is_distinct(c))
+
+
+def edge_pre(pre):
+    def make():
+        c = pre_of(pre)()
+        inner = c["present"]
+        c["present"] = lambda c, st: (inner(c, st) and st[0]["kept"] <= pre and (pre > 0 or not want(c)[0].any()) and is_distinct(c))
+        return c
+    return make
+
+
+def edge_thresh(thresh, rotated=True):
+    """300 rows, POST 300: at or below 0 every later box is suppressed by an overlapping earlier one (below 0 by the
+    first, so every chunk is dead before it is read); at 1 and above, NaN included, nothing is (up to an IoU that rounds
+    above 1), and the kept list grows by whole chunks"""
+    def make():
+        p, sc = pool()
+        t = F(thresh)
+
+        def present(c, st):
+            k, n = st[0]["kept"], 300
+            return (st[0]["candidates"] == n and (k == 1 if t < 0 else 1 < k < 100 if t == 0 else n - 5 <= k <= n if t == 1 else k == n)
+                    and is_distinct(c))
+        return stacked(p[:300], sc[:300], post=300, thresh=thresh, rotated=rotated, present=present)
+    return make
+
+
+STRAY_Z = F(777)      # the strays' z: no row of a sample has it
+STRAYS_F32 = np.array([65535, 65536, -1, 0.5, np.nan, 1e9], F)
+STRAYS_I64 = np.array([65535, 65536, -1, 2 ** 32, -2 ** 63, 10 ** 9], np.int64)      # 2^32: sample 0 if cut to 32 bits
+
+
+def many_samples(form):
+    """B = 65535 samples of 2 rows: a pool row and, in every third sample, the same box moved by 0.25 m (the pair
+    overlaps: 1 kept), else another pool row.  form: "f32" / "i64" (stacked, interleaved by a permutation, 6 strays with
+    score 2.0) or "dense" ((65535, 2, 7))"""
+    def make():
+        B = seq.BATCH_MAX
+        p, sc = pool()
+        s = np.arange(B)
+        i, j = s % 4608, (s * 7 + 1 + s // 4608) % 4608
+        box = np.stack([p[i], p[j]], 1)
+        near = s % 3 == 0
+        box[near, 1] = box[near, 0]
+        box[near, 1, 0] += F(0.25)
+        cls = np.stack([sc[i] - HALF, sc[j] - F(1)], 1)[..., None]
+
+        def present(c, st):
+            rois, scores, _ = want(c)
+            kept = np.array([o["kept"] for o in st])
+            return (c["B"] == B == 65535 and all(o["candidates"] == 2 for o in st) and (kept == 1).any() and (kept == 2).any()
+                    and set(kept) == {1, 2} and not (rois[..., 2] == STRAY_Z).any() and not (scores == 2).any()
+                    and c["box"].size // 7 == (2 * B if form == "dense" else 131076))
+        if form == "dense":
+            return dict(box=np.ascontiguousarray(box, F), cls=np.ascontiguousarray(cls, F), batch_index=None, B=B, pre=BIG, post=2,
+                        thresh=0.7, rotated=True, present=present)
+        stray = p[:6].copy()
+        stray[:, 2] = STRAY_Z
+        box, cls = np.concatenate([box.reshape(-1, 7), stray]), np.concatenate([cls.reshape(-1), np.full(6, 2.0, F)])
+        bidx = np.concatenate([np.repeat(s, 2).astype(F), STRAYS_F32]) if form == "f32" else np.concatenate([np.repeat(s, 2), STRAYS_I64])
+        perm = np.random.default_rng(9).permutation(len(box))
+        return stacked(box[perm], cls[perm], B=B, bidx=bidx[perm], post=2, thresh=0.7, present=present)
+    return make
+
+
+def wide(box_cols=7, cls_cols=1):
+    """130 rows, POST 70, one of the two widths at its limit of 4096"""
+    def make():
+        p, sc = pool()
+        n = 130
+        rng = np.random.default_rng(10)
+        box = np.concatenate([p[:n], rng.random((n, box_cols - 7)).astype(F)], 1)
+        cls = (rng.random((n, cls_cols)).astype(F) * HALF - F(1))      # below every maximum set here
+        r = np.arange(n)
+        top = (sc[:n] - HALF).astype(F)
+        if cls_cols > 1:
+            cls[r[0::3], 4000 + r[0::3] % 96] = top[0::3]      # the maximum far out
+            cls[1::3, 0] = top[1::3]                           # ... in column 0
+            cls[2::3, 5] = cls[2::3, 4095] = top[2::3]         # ... twice: the lower column takes it
+        else:
+            cls[:, 0] = top
+
+        def present(c, st):
+            k = st[0]["kept"]
+            rois, _, labels = want(c)
+            lab = set(labels[0, :k])
+            return (k == 70 and c["box"].shape[1] == box_cols and c["cls"].shape[1] == cls_cols and 4096 in (box_cols, cls_cols)
+                    and rois[0, :k, -1].all()
+                    and (cls_cols == 1 or (1 in lab and 6 in lab and 4096 not in lab and max(lab) > 4000 and lab - {1, 6} != set())))
+        return stacked(box, cls, post=70, thresh=0.85, present=present)
+    return make
+
+
+EDGE_CASES = {
+    "logits": logits(), "logits axis-aligned": logits(False), "logits K 3": logits_k3, "zeros and denormals": zeros_and_denormals,
+    "non-finite boxes": non_finite(True, ROTATED_COLUMNS), "non-finite boxes axis-aligned": non_finite(False),
+    "POST 1024 full": post_full,
+    "PRE 0": edge_pre(0), "PRE 1": edge_pre(1), "PRE 64": edge_pre(64), "PRE 65": edge_pre(65),
+    "thresh -1": edge_thresh(-1.0), "thresh 0": edge_thresh(0.0), "thresh 1": edge_thresh(1.0), "thresh NaN": edge_thresh(np.nan),
+    "thresh +inf": edge_thresh(np.inf), "thresh -1 axis-aligned": edge_thresh(-1.0, False),
+    "thresh +inf axis-aligned": edge_thresh(np.inf, False),
+    "B 65535 stacked": many_samples("f32"), "B 65535 stacked int64": many_samples("i64"), "B 65535 dense": many_samples("dense"),
+    "4096 box columns": wide(box_cols=4096), "4096 class columns": wide(cls_cols=4096),
+}
+assert not set(EDGE_CASES) & set(CASES)
+# no order is open on these (is_distinct, asserted by each): the reference's own path must give the same bits.  The
+# B 65535 cases are distinct too but stay out: that path is a Python loop over the samples
+EDGE_DISTINCT = ["logits", "logits axis-aligned", "logits K 3", "POST 1024 full", "PRE 0", "PRE 1", "PRE 64", "PRE 65",
+                 "thresh -1", "thresh 0", "thresh 1", "thresh -1 axis-aligned"]
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
-    c = CASES[name]()
+    c = (CASES[name] if name in CASES else EDGE_CASES[name])()
     for k in ("box", "cls", "batch_index"):
         if c[k] is not None:
             c[k].setflags(write=False)

@@ -9,6 +9,7 @@ the reference leaves it open (equal scores by ascending row, the lowest class am
   proposals_chunked(...)   the same results by the kernel's own walk: chunks of CHUNK candidates against a kept list dealt
                            round-robin to WAVES wavefronts, then among themselves, resolved in order, stopping at the
                            POST-th survivor inside a chunk; `fault` breaks it in one named way (FAULTS)
+  proposals(key_fault=..)  the first restatement over one named wrong sort key (KEY_FAULTS)
   parent_walk(...)         the keep list of one sample, for the tools and tests that need the positions
 
 Boxes are (n, 7 + C) float32, class values (n, K) float32.  `batch_index` None means the dense form ((B, N, .) inputs).
@@ -25,6 +26,7 @@ F = np.float32
 CHUNK, WAVES, POST_MAX, BATCH_MAX = 64, 4, 1024, 65535      # csrc/proposals.hip
 FAULTS = ("first wavefront's share only", "chunk not tested against itself", "suppressed candidates still suppress",
           "kept list restarts per chunk")
+KEY_FAULTS = ("negatives not inverted", "-0 below +0", "denormals are zero", "NaN last")      # wrong sort keys
 
 
 def score_label(cls):
@@ -39,14 +41,20 @@ def score_label(cls):
     return best.astype(F), at
 
 
-def descending_bits(s):
-    """uint32 whose ascending order is the descending order of the scores: NaN first, -0 == +0"""
+def descending_bits(s, fault=None):
+    """uint32 whose ascending order is the descending order of the scores: NaN first, -0 == +0; `fault` builds one
+    named wrong key instead (KEY_FAULTS)"""
+    assert fault is None or fault in KEY_FAULTS, fault
     s = np.asarray(s, F).copy()
-    s[s == 0] = 0
+    if fault != "-0 below +0":
+        s[s == 0] = 0
+    if fault == "denormals are zero":
+        s[np.abs(s) < np.finfo(F).tiny] = 0
     u = s.view(np.uint32).astype(np.uint64)
-    asc = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
+    neg = (u ^ 0x80000000) if fault == "negatives not inverted" else (~u & 0xFFFFFFFF)
+    asc = np.where(u & 0x80000000, neg, u | 0x80000000)
     out = (~asc) & 0xFFFFFFFF
-    out[np.isnan(s)] = 0
+    out[np.isnan(s)] = 0xFFFFFFFF if fault == "NaN last" else 0
     return out.astype(np.uint64)
 
 
@@ -60,26 +68,30 @@ def sample_of(batch_index, n, B, rows_per_sample=None):
     return np.where(ok, np.nan_to_num(b, nan=0.0, posinf=0.0, neginf=0.0), B).astype(np.int64)
 
 
-def candidates(score, sample, B, pre):
+def candidates(score, sample, B, pre, key_fault=None):
     """per sample the rows of its min(pre, rows) highest scores, in walk order"""
-    key = (sample.astype(np.uint64) << np.uint64(32)) | descending_bits(score)
+    key = (sample.astype(np.uint64) << np.uint64(32)) | descending_bits(score, key_fault)
     order = np.argsort(key, kind="stable")
-    ks = sample[order]
-    return [order[ks == s][:pre] for s in range(B)]
+    cut = np.searchsorted(sample[order], np.arange(B + 1))      # the stable order is grouped by sample
+    return [order[cut[s]:min(cut[s + 1], cut[s] + pre)] for s in range(B)]
 
 
-def iou_normal(a, b):
-    """iou_normal of csrc/iou_bev.h for all pairs, float32 in the written order -> (na, nb)"""
+def iou_normal(a, b, nan_propagates=False):
+    """iou_normal of csrc/iou_bev.h for all pairs, float32 in the written order -> (na, nb).  fmaxf / fminf return the
+    other operand when one is a NaN, as np.fmax / np.fmin do; np.maximum / np.minimum (nan_propagates, kept to show the
+    difference) hand the NaN on"""
     a, b = np.asarray(a, F)[:, None, :], np.asarray(b, F)[None, :, :]
     two = F(2)
-    left = np.maximum(a[..., 0] - a[..., 3] / two, b[..., 0] - b[..., 3] / two)
-    right = np.minimum(a[..., 0] + a[..., 3] / two, b[..., 0] + b[..., 3] / two)
-    top = np.maximum(a[..., 1] - a[..., 4] / two, b[..., 1] - b[..., 4] / two)
-    bottom = np.minimum(a[..., 1] + a[..., 4] / two, b[..., 1] + b[..., 4] / two)
-    w, h = np.maximum(right - left, F(0)), np.maximum(bottom - top, F(0))
-    inter = w * h
-    sa, sb = a[..., 3] * a[..., 4], b[..., 3] * b[..., 4]
-    return (inter / np.maximum(sa + sb - inter, F(1e-8))).astype(F)
+    hi, lo = (np.maximum, np.minimum) if nan_propagates else (np.fmax, np.fmin)
+    with np.errstate(all="ignore"):
+        left = hi(a[..., 0] - a[..., 3] / two, b[..., 0] - b[..., 3] / two)
+        right = lo(a[..., 0] + a[..., 3] / two, b[..., 0] + b[..., 3] / two)
+        top = hi(a[..., 1] - a[..., 4] / two, b[..., 1] - b[..., 4] / two)
+        bottom = lo(a[..., 1] + a[..., 4] / two, b[..., 1] + b[..., 4] / two)
+        w, h = hi(right - left, F(0)), hi(bottom - top, F(0))
+        inter = w * h
+        sa, sb = a[..., 3] * a[..., 4], b[..., 3] * b[..., 4]
+        return (inter / hi(sa + sb - inter, F(1e-8))).astype(F)
 
 
 def pair_iou(a, b, rotated):
@@ -169,20 +181,20 @@ def _flat(box, cls, batch_index):
     return box, cls, per
 
 
-def survivors(box, cls, B, pre, post, thresh, rotated=True, batch_index=None, walk=parent_walk, **kw):
+def survivors(box, cls, B, pre, post, thresh, rotated=True, batch_index=None, walk=parent_walk, key_fault=None, **kw):
     """per sample the rows of the survivors, in order"""
     box, cls, per = _flat(box, cls, batch_index)
     score, _ = score_label(cls)
     sample = sample_of(batch_index, len(box), B, per)
     out = []
-    for rows in candidates(score, sample, B, pre):
+    for rows in candidates(score, sample, B, pre, key_fault):
         out.append(rows[walk(box[rows], thresh, rotated, post, **kw)] if len(rows) else rows)
     return out
 
 
-def proposals(box, cls, B, pre, post, thresh, rotated=True, batch_index=None):
+def proposals(box, cls, B, pre, post, thresh, rotated=True, batch_index=None, key_fault=None):
     """-> rois (B, post, 7 + C) float32, roi_scores (B, post) float32, roi_labels (B, post) int64"""
-    rows_of = survivors(box, cls, B, pre, post, thresh, rotated, batch_index)
+    rows_of = survivors(box, cls, B, pre, post, thresh, rotated, batch_index, key_fault=key_fault)
     box, cls, _ = _flat(box, cls, batch_index)
     return _assemble(box, cls, B, post, rows_of)
 

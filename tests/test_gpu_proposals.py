@@ -1,5 +1,6 @@
 """GPU: modest_amd.ops.proposals and the drop-in proposal_layer (csrc/proposals.hip) against the numpy
-restatement tests/proposals_seq.py, bit for bit on all three outputs, on the cases of tests/proposals_cases.py (each asserts
+restatement tests/proposals_seq.py, bit for bit on all three outputs, on the cases of tests/proposals_cases.py (CASES and EDGE_CASES: logit scores, zeros and
+denormals, non-finite boxes, POST 1024 reached, PRE 0 - 65, thresholds -1 - +inf and NaN, B = 65535, 4096 columns; each asserts
 its edge in tests/test_proposals_cpu.py) and on the scenes recorded from the reference's own proposal_layer
 (tests/golden/proposals.npz).  Rows whose heading the device's double cos / sin rounds differently from the host's are taken
 out of the inputs first and counted (at most 0.1 % of the rows, the MAX_DROPPED of tests/test_gpu_iou3d.py).  On the cases
@@ -28,12 +29,14 @@ DEV = torch.device("cuda")
 
 def trig_differs(h):
     """rows whose heading the device's double cos / sin, rounded to float32, evaluates differently from the host's double
-    libm (tests/test_gpu_iou3d.py:_trig_differs)"""
+    libm (tests/test_gpu_iou3d.py:_trig_differs); a NaN on both sides (a non-finite heading) is no difference"""
     h = np.ascontiguousarray(h, np.float32).reshape(-1)
     hd = torch.from_numpy(h.copy()).to(DEV).double()
     dev = torch.stack([torch.cos(hd).float(), torch.sin(hd).float(), torch.cos(-hd).float(), torch.sin(-hd).float()], 1).cpu().numpy()
-    host = np.array([[math.cos(v), math.sin(v), math.cos(-v), math.sin(-v)] for v in h.astype(np.float64)]).astype(np.float32)
-    return (dev != host).any(1)
+    trig = lambda f, v: f(v) if math.isfinite(v) else math.nan      # noqa: E731  (math.cos(inf) raises, C's gives NaN)
+    host = np.array([[trig(math.cos, v), trig(math.sin, v), trig(math.cos, -v), trig(math.sin, -v)]
+                     for v in h.astype(np.float64)]).astype(np.float32)
+    return ((dev != host) & ~(np.isnan(dev) & np.isnan(host))).any(1)
 
 
 def without_dropped(c):
@@ -81,7 +84,10 @@ def want_of(c):
                                                            c["rotated"], c["batch_index"])
 
 
-@pytest.mark.parametrize("name", list(cases.CASES))
+ALL = list(cases.CASES) + list(cases.EDGE_CASES)
+
+
+@pytest.mark.parametrize("name", ALL)
 def test_cases_against_the_restatement(name):
     """into outputs the test filled with a sentinel: the same objects come back, every element written, the
     restatement's bits"""
@@ -99,9 +105,9 @@ def test_cases_against_the_restatement(name):
 
 
 def test_dropped_rows_are_few():
-    """the rows taken out over all cases: counted, printed, at most 0.1 %"""
+    """the rows taken out over all cases of both registries: counted, printed, at most 0.1 %"""
     rows = dropped = 0
-    for name in cases.CASES:
+    for name in ALL:
         _, n, d = without_dropped(cases.case(name))
         rows, dropped = rows + n, dropped + d
     print(f"rows whose device trig differs from the host's: {dropped} of {rows}")
@@ -130,12 +136,17 @@ def parent_path(box_preds, cls_preds, batch_size, pre, post, thresh, nms_type, b
     return rois, roi_scores, roi_labels + 1
 
 
-DISTINCT = [n for n in cases.CASES if cases.is_distinct(cases.case(n))]
+DISTINCT = [n for n in cases.CASES if cases.is_distinct(cases.case(n))] + cases.EDGE_DISTINCT
 
 
 def test_enough_cases_leave_no_order_open():
-    assert len(DISTINCT) >= 25 and {"past every capacity", "dense", "3 samples", "POST inside a chunk", "fewer than POST",
-                                    "thresh 0.7 axis-aligned", "64 rows", "65 rows"} <= set(DISTINCT)
+    assert len(DISTINCT) >= 25 + 12 and {"past every capacity", "dense", "3 samples", "POST inside a chunk", "fewer than POST",
+                                         "thresh 0.7 axis-aligned", "64 rows", "65 rows"} <= set(DISTINCT)
+    # the edges: negative scores, the full kept list, PRE down to no candidate, the finite thresholds
+    assert {"logits", "logits axis-aligned", "logits K 3", "POST 1024 full", "PRE 0", "PRE 1", "PRE 64", "PRE 65", "thresh -1", "thresh 0",
+            "thresh 1", "thresh -1 axis-aligned"} <= set(DISTINCT)
+    assert all(cases.is_distinct(cases.case(n)) for n in cases.EDGE_DISTINCT)
+    assert not any(cases.case(n)["B"] > 3 for n in DISTINCT)      # the path before loops over the samples in Python
 
 
 @pytest.mark.parametrize("name", DISTINCT)
@@ -184,6 +195,18 @@ def test_a_large_call_then_a_small_one_on_the_same_workspace():
     few = cases.case("fewer than POST")
     assert seq.same(run(few, workspace=ws), run(few))
     assert seq.same(run(small, workspace=ws), want_small)
+
+
+def test_all_samples_then_a_small_call_on_the_same_workspace():
+    """B = 65535: 65 535 workgroups, 48 key bits; then one sample of 63 rows, whose segment search meets only its own keys"""
+    big, small = cases.case("B 65535 stacked"), cases.case("63 rows")
+    ws = torch.empty((ops.proposals_workspace_bytes(len(big["box"])),), dtype=torch.uint8, device=DEV)
+    ws.fill_(0xFF)
+    assert ops.proposals_workspace_bytes(len(small["box"])) < ws.numel()
+    want_big, want_small = run(big), run(small)
+    assert seq.same(run(big, workspace=ws), want_big)
+    assert seq.same(run(small, workspace=ws), want_small)
+    assert seq.same(run(big, workspace=ws), want_big)
 
 
 def test_a_side_stream():
@@ -255,5 +278,21 @@ def test_limits_name_themselves():
     cfg = dict(MULTI_CLASSES_NMS=False, NMS_TYPE="nms_gpu", NMS_PRE_MAXSIZE=9000, NMS_POST_MAXSIZE=seq.POST_MAX + 1, NMS_THRESH=0.7)
     with pytest.raises(ValueError, match="1024"):
         head.proposal_layer(dict(batch_size=1, batch_box_preds=box, batch_cls_preds=cls, batch_index=bidx), cfg)
+    # 4096 box columns and 4096 class columns work (test_cases_against_the_restatement runs both cases), 4097 are refused
+    for name in ("4096 box columns", "4096 class columns"):
+        w = cases.case(name)
+        wbox, wcls, wbidx = device_inputs(w)
+        assert 4096 in (wbox.shape[1], wcls.shape[1])
+        ok = ops.proposals(wbox, wcls, 1, w["pre"], w["post"], w["thresh"], batch_index=wbidx)
+        assert seq.same(tuple(t.cpu().numpy() for t in ok), cases.want(w)), name
+    wide = torch.zeros((len(c["box"]), 4097), device=DEV)
+    wide[:, :7] = box
+    with pytest.raises(ModestHipError, match="4096"):
+        ops.proposals(wide, cls, 1, 9000, 10, 0.7, batch_index=bidx)
+    with pytest.raises(ModestHipError, match="4096"):
+        ops.proposals(box, wide, 1, 9000, 10, 0.7, batch_index=bidx)
+    # B = 65535 itself works
+    many = cases.case("B 65535 dense")
+    assert many["B"] == seq.BATCH_MAX and seq.same(run(many), cases.want(many))
     # a refused call leaves the next one right
     assert seq.same(run(c), cases.want(c))

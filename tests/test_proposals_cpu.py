@@ -49,6 +49,52 @@ def test_every_case_holds_its_edge_and_both_restatements_agree(name):
         assert (want[2][s, :k] >= 1).all() and (want[2][s, :k] <= c["cls"].shape[-1]).all()
 
 
+def both(c):
+    """stats, and both restatements agreeing on the case; the padding is zeros, zeros and ones (all samples at once)"""
+    rows_of = []
+    st = cases.stats_of(c, rows_of)
+    want = cases.want(c)
+    assert want[0].shape == (c["B"], c["post"], c["box"].shape[-1]) and want[2].dtype == np.int64 and want[1].dtype == F
+    box, cls, _ = seq._flat(c["box"], c["cls"], c["batch_index"])
+    got = seq._assemble(box, cls, c["B"], c["post"], rows_of)            # proposals_chunked, its walk made once
+    assert seq.same(got, want), "\n".join(seq.describe(got, want))
+    pad = np.arange(c["post"])[None, :] >= np.array([one["kept"] for one in st])[:, None]
+    assert not want[0][pad].any() and not want[1][pad].any() and (want[2][pad] == 1).all()
+    assert (want[2] >= 1).all() and (want[2] <= c["cls"].shape[-1]).all()
+    return st
+
+
+@pytest.mark.parametrize("name", list(cases.EDGE_CASES))
+def test_every_edge_case_holds_its_edge_and_both_restatements_agree(name):
+    """the three B = 65535 cases take 5 to 6.5 s each on the build machine (one oracle walk and one chunked walk per
+    sample, the padding of all samples at once); candidates() splits their 131 076 rows in 0.1 s, by one mask per sample
+    it took 6.7 s each time it was called"""
+    c = cases.case(name)
+    st = both(c)
+    assert c["present"](c, st), st[:3]
+    if name in cases.EDGE_DISTINCT:
+        assert cases.is_distinct(c)
+
+
+def test_iou_normal_drops_a_nan_as_fmaxf_does(monkeypatch):
+    """the axis-aligned pair test of the chunked walk on non-finite boxes: with np.maximum / np.minimum, which hand a NaN
+    on, it keeps other boxes than the C walk of oracle/iou3d_oracle.c (fmaxf / fminf); with np.fmax / np.fmin the same"""
+    c = cases.case("non-finite boxes axis-aligned")
+    assert seq.same(chunked(c), cases.want(c))
+    a = np.array([[0, 0, 0, 2, 2, 1, 0]], F)
+    b = np.array([[np.nan, 0, 0, 2, 2, 1, 0], [0, 0, 0, np.nan, 2, 1, 0], [0, 0, 0, np.inf, 2, 1, 0], [0.5, 0, 0, 2, 2, 1, 0]], F)
+    # x NaN: fmaxf / fminf leave a's edges, 4 / (4 + 4 - 4); dx NaN: the union is NaN, fmaxf gives 1e-8; dx inf: 4 / inf
+    v = seq.iou_normal(a, b)[0]
+    assert v[0] == 1 and v[1] > 1e8 and v[2] == 0 and v[3] == F(0.6) and np.isnan(seq.iou_normal(a, b, nan_propagates=True)[0, :2]).all()
+    import functools
+    monkeypatch.setattr(seq, "iou_normal", functools.partial(seq.iou_normal, nan_propagates=True))
+    assert not seq.same(chunked(c), cases.want(c))
+    for name in cases.CASES:                       # finite boxes: either form gives the same
+        c = cases.case(name)
+        if not c["rotated"] and c["B"] == 1:
+            assert seq.same(chunked(c), cases.want(c)), name
+
+
 def test_the_cases_cover_the_list():
     kept = {n: [s["kept"] for s in cases.stats_of(cases.case(n))] for n in ("fewer than POST", "POST inside a chunk", "PRE cuts a tie")}
     assert kept["fewer than POST"] == [44] and kept["POST inside a chunk"] == [100]
@@ -82,15 +128,33 @@ def test_the_cases_cover_the_list():
     for line in ("constexpr int PW_WAVES = 4;", "constexpr int PW_CHUNK = 64;", "constexpr int PW_POST_MAX = 1024;",
                  "constexpr int PROP_MAX_BATCH = 65535;"):
         assert line in text, line
+    # the edges: every limit run, the rows all padding, thresholds on both sides of every IoU
+    edge = [cases.case(n) for n in cases.EDGE_CASES]
+    assert seq.BATCH_MAX in {c["B"] for c in edge} and seq.POST_MAX in {c["post"] for c in edge}
+    assert 4096 in {c["box"].shape[-1] for c in edge} and 4096 in {c["cls"].shape[-1] for c in edge}
+    assert {0, 1, seq.CHUNK, seq.CHUNK + 1} <= {c["pre"] for c in edge}
+    assert any(c["thresh"] < 0 for c in edge) and any(np.isnan(c["thresh"]) for c in edge) and any(np.isposinf(c["thresh"]) for c in edge)
+    assert {0.0, 1.0} <= {c["thresh"] for c in edge}
+    assert any(c["batch_index"] is None and c["B"] == seq.BATCH_MAX for c in edge)
+    assert {c["batch_index"].dtype for c in edge if c["B"] == seq.BATCH_MAX and c["batch_index"] is not None} == {np.dtype(F), np.dtype(np.int64)}
+    assert any((c["cls"] < 0).sum() > 100 for c in edge) and any(not np.isfinite(c["box"][..., :7]).all() for c in edge)
+    assert seq.same(cases.want(cases.case("B 65535 stacked")), cases.want(cases.case("B 65535 stacked int64")))
+    assert seq.same(cases.want(cases.case("B 65535 stacked")), cases.want(cases.case("B 65535 dense")))     # the strays change nothing
 
 
 # fault -> cases on which the chunked walk, so broken, gives other outputs
 SEEN_BY = {
-    "first wavefront's share only": ["1000 rows", "POST 512", "past every capacity", "dense", "thresh 0.7 axis-aligned"],
-    "chunk not tested against itself": ["63 rows", "64 rows", "exact duplicates", "equal scores"],
-    "suppressed candidates still suppress": ["thresh 0.7", "3 samples"],
-    "kept list restarts per chunk": ["129 rows", "1000 rows", "fewer than POST", "3 samples axis-aligned"],
+    "first wavefront's share only": ["1000 rows", "POST 512", "past every capacity", "dense", "thresh 0.7 axis-aligned",
+                                     "POST 1024 full", "logits", "thresh 0", "non-finite boxes"],
+    "chunk not tested against itself": ["63 rows", "64 rows", "exact duplicates", "equal scores", "PRE 64", "PRE 65", "thresh -1",
+                                        "thresh 1", "4096 class columns"],
+    "suppressed candidates still suppress": ["thresh 0.7", "3 samples", "non-finite boxes axis-aligned"],
+    "kept list restarts per chunk": ["129 rows", "1000 rows", "fewer than POST", "3 samples axis-aligned", "logits",
+                                     "POST 1024 full", "non-finite boxes axis-aligned", "thresh -1 axis-aligned"],
 }
+# wrong key -> the case on which the restatement, sorting by it, gives other outputs
+KEY_SEEN_BY = {"negatives not inverted": "logits", "-0 below +0": "zeros and denormals", "denormals are zero": "zeros and denormals",
+               "NaN last": "NaN scores"}
 
 
 @pytest.mark.parametrize("fault", list(seq.FAULTS))
@@ -99,6 +163,17 @@ def test_every_fault_shows_on_its_cases(fault):
     for name in SEEN_BY[fault]:
         c = cases.case(name)
         assert not seq.same(chunked(c, fault), cases.want(c)), (fault, name)
+
+
+@pytest.mark.parametrize("fault", list(seq.KEY_FAULTS))
+def test_every_wrong_key_shows_on_its_case(fault):
+    assert set(KEY_SEEN_BY) == set(seq.KEY_FAULTS) and not set(seq.KEY_FAULTS) & set(seq.FAULTS)
+    c = cases.case(KEY_SEEN_BY[fault])
+    args = (c["box"], c["cls"], c["B"], c["pre"], c["post"], c["thresh"], c["rotated"], c["batch_index"])
+    assert seq.same(seq.proposals(*args, key_fault=None), cases.want(c))
+    assert not seq.same(seq.proposals(*args, key_fault=fault), cases.want(c)), fault
+    with pytest.raises(AssertionError):
+        seq.descending_bits(np.zeros(1, F), fault="no such key")
 
 
 def test_tie_rules():
