@@ -1192,6 +1192,68 @@ int modest_proposals(int64_t n_rows, int batch_size, int64_t rows_per_sample, co
                      float *roi_scores_dev, int64_t *roi_labels_dev, void *workspace_dev, int64_t workspace_bytes,
                      void *stream);
 
+/* ---- a32 RoI target assignment (RoIHeadTemplate.assign_targets over ProposalTargetLayer.forward) ---------
+ * Two calls, because the reference draws its samples from the host's generators with the list lengths as arguments.  No
+ * context, no device allocation.  Every buffer [dev] and contiguous unless said otherwise.
+ *   rois        (batch_size, n_rois, roi_cols = 7 + C) float32;   roi_scores (batch_size, n_rois) float32;
+ *   roi_labels  (batch_size, n_rois) int64;
+ *   gt          (batch_size, n_gt, roi_cols + 1) float32 by three strides counted in elements; the last column is the class.
+ *
+ * modest_roi_targets_match: BLOCKING -- one launch, one stream synchronise.  Per sample:
+ *   trim      the valid gts are rows 0 .. k, k the last row whose float32 sum over all columns, added in column order, is
+ *             not == 0 (a NaN sum is not), k = 0 if there is none; with n_gt = 0 the sample has one box of zeros;
+ *   match     per roi the 3-D IoU with every valid gt: overlap_bev (as modest_boxes_overlap_bev) times
+ *             clamp(min(tops) - max(bottoms), min = 0), over max(va + vb - overlap, 1e-6), volumes (dx * dy) * dz, all in
+ *             float32; the maximum and its gt row -- the LOWEST row among equal maxima, a NaN above every number, the
+ *             first NaN.  With by_class != 0 only gts whose (int64) class equals the roi's label compete; a roi without a
+ *             competitor has maximum 0 and row 0;
+ *   lists     in ascending roi order, list 0 fg: iou >= fg_thresh; list 1 hard: iou < reg_fg_thresh and
+ *             iou >= bg_thresh_lo; list 2 easy: iou < bg_thresh_lo.  A NaN is in none; a roi may be in fg and hard.
+ * The maxima, rows and lists stay in the workspace; the (batch_size, 3) int32 list lengths are written by the kernel into
+ * counts_pinned_host (pinned host memory the device can address) and are valid when the call returns.
+ *
+ * modest_roi_targets_sample: enqueue only, nothing read back.  picks (batch_size, roi_per_image, 2) int32 in pinned host
+ * or device memory: list (0 fg, 1 hard, 2 easy) and position in that list, of the workspace the match call with the same
+ * batch_size and n_rois filled.  Slot (b, m) resolves its pick to roi row r and gt row g and writes, of every output every
+ * element:
+ *   out_rois (B, M, roi_cols) = rois[b, r];  out_roi_scores, out_roi_labels (int64), out_gt_iou (B, M);
+ *   out_gt_of_rois_src (B, M, roi_cols + 1) = gt[b, g];  out_reg_valid (B, M) int64 = iou > reg_fg_thresh;
+ *   out_cls_labels (B, M): score_type 0 (cls) int64 -- 1 if iou > cls_fg, -1 if cls_bg < iou < cls_fg, else 0 (a NaN: 0);
+ *             score_type 1 (roi_iou) float32 -- 1 if iou > cls_fg, 0 if iou < cls_bg, else (iou - cls_bg) / fg_minus_bg,
+ *             one division by the caller's float32 of the double difference (a NaN stays);
+ *   out_gt_of_rois (B, M, roi_cols + 1), the canonical form: ry = remainder(roi[6], 2 pi); centre and ry subtracted;
+ *             (x, y, z) times [[c, s, 0], [-s, c, 0], [0, 0, 1]] with c, s = cos, sin of -ry in double rounded once, every
+ *             product rounded before the sums; the heading folded into [-pi / 2, pi / 2]; other columns as in gt.
+ * A pick that names no list, or a position outside its list, writes a slot of zeros; nothing is read out of bounds.
+ * Limits (the call fails and launches nothing): roi_cols in [7, 4096], batch_size <= 65535, roi_per_image >= 1, at most
+ * 2^31 - 1 roi rows, gt rows and output rows in a call.
+ * workspace 8-byte aligned, modest_roi_targets_workspace_bytes(batch_size, n_rois) bytes (20 bytes a roi and 12 a sample,
+ * each of the six arrays rounded up to 256), need not be initialised.
+ * Lifetime of picks: the sample call returns before its kernel has read them.  A pinned host table is read where it lies,
+ * so the caller keeps it mapped and unwritten until the stream has passed the call.  A later match call on the SAME stream
+ * synchronises it, after which the table may be written again; work on another stream needs a table of its own.  An
+ * allocator that caches pinned blocks and knows nothing of this kernel (PyTorch's) must not get the block back earlier.
+ * modest_roi_targets_gt_tile: the gts a match workgroup stages in LDS at a time (a test builds its shapes around it).
+ * modest_roi_targets_workspace_offsets: the byte offsets in the workspace of the six arrays a match call leaves, into
+ * offsets_host[6]: counts (batch_size, 3) int32; maxima (batch_size, n_rois) float32; gt rows (batch_size, n_rois) int32;
+ * the fg, hard and easy lists, each (batch_size, n_rois) int32 of which a sample's first count entries are valid.  For
+ * tests and tools that read the lists back; needs no device.                                                              */
+int modest_roi_targets_gt_tile(void);
+int64_t modest_roi_targets_workspace_bytes(int batch_size, int n_rois);
+int modest_roi_targets_workspace_offsets(int batch_size, int n_rois, int64_t *offsets_host);
+int modest_roi_targets_match(int batch_size, int n_rois, int n_gt, const float *rois_dev, int roi_cols,
+                             const int64_t *roi_labels_dev, const float *gt_dev, int64_t gt_stride_b, int64_t gt_stride_n,
+                             int64_t gt_stride_c, float fg_thresh, float bg_thresh_lo, float reg_fg_thresh, int by_class,
+                             void *workspace_dev, int64_t workspace_bytes, int32_t *counts_pinned_host, void *stream);
+int modest_roi_targets_sample(int batch_size, int n_rois, int n_gt, int roi_per_image, const int32_t *picks,
+                              const float *rois_dev, int roi_cols, const float *roi_scores_dev,
+                              const int64_t *roi_labels_dev, const float *gt_dev, int64_t gt_stride_b, int64_t gt_stride_n,
+                              int64_t gt_stride_c, float reg_fg_thresh, float cls_fg_thresh, float cls_bg_thresh,
+                              float fg_minus_bg, int score_type, const void *workspace_dev, int64_t workspace_bytes,
+                              float *out_rois_dev, float *out_gt_of_rois_dev, float *out_gt_iou_dev,
+                              float *out_roi_scores_dev, int64_t *out_roi_labels_dev, int64_t *out_reg_valid_dev,
+                              void *out_cls_labels_dev, float *out_gt_of_rois_src_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

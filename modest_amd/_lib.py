@@ -147,6 +147,14 @@ SIGNATURES = {
     "modest_proposals_workspace_bytes": (C.c_int64, [C.c_int64]),
     "modest_proposals": (C.c_int, [C.c_int64, C.c_int, C.c_int64, VP, C.c_int, VP, C.c_int, VP, C.c_int, C.c_int, C.c_int,
                                    C.c_float, C.c_int, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_roi_targets_gt_tile": (C.c_int, []),
+    "modest_roi_targets_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "modest_roi_targets_workspace_offsets": (C.c_int, [C.c_int, C.c_int, VP]),
+    "modest_roi_targets_match": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, C.c_int, VP, VP, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_float, C.c_float, C.c_float, C.c_int, VP, C.c_int64, VP, VP]),
+    "modest_roi_targets_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, C.c_int64,
+                                            C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, VP,
+                                            C.c_int64, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

@@ -1665,3 +1665,225 @@ def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int,
                                    int(bool(rotated)), rois.data_ptr(), scores.data_ptr(), labels.data_ptr(),
                                    workspace.data_ptr(), workspace.numel(), _stream()), "modest_proposals")
     return rois, scores, labels
+
+
+# --------------------------------------------------------------------------- RoI target assignment
+ROI_LISTS = ("fg", "hard", "easy")          # list ids of a pick, and the order of a sample's three counts
+ROI_SCORE_TYPES = {"cls": 0, "roi_iou": 1}
+ROI_BATCH_MAX = 65535                       # samples per call
+ROI_COLS_MAX = 4096                         # 7 + C
+
+
+def roi_targets_gt_tile() -> int:
+    """gts a match workgroup stages in LDS at a time"""
+    return int(load().modest_roi_targets_gt_tile())
+
+
+def roi_targets_workspace_bytes(batch_size: int, n_rois: int) -> int:
+    nb = int(load().modest_roi_targets_workspace_bytes(int(batch_size), int(n_rois)))
+    if nb < 0:
+        check(nb, "modest_roi_targets_workspace_bytes")
+    return nb
+
+
+def _cfg_get(cfg, name, *default):
+    if isinstance(cfg, dict):
+        return cfg.get(name, *default) if default else cfg[name]
+    return getattr(cfg, name, *default)
+
+
+def roi_target_draws(counts, cfg, np_random=None, generator=None, sample=0):
+    """the picks of one sample from its (fg, hard, easy) counts: exactly the reference's calls in the reference's order
+    (subsample_rois, sample_bg_inds of proposal_target_layer.py) on numpy's and torch's CPU generators
+    -> (ROI_PER_IMAGE, 2) int32 of (list, position)"""
+    npr = np.random if np_random is None else np_random
+    M = int(_cfg_get(cfg, "ROI_PER_IMAGE"))
+    nf, nh, ne = (int(v) for v in counts)
+    nb = nh + ne
+    fg_per = int(np.round(_cfg_get(cfg, "FG_RATIO") * M))
+
+    def randint(high, n):
+        return torch.randint(low=0, high=high, size=(n,), generator=generator).long().numpy()
+
+    def bg(n):
+        if nh > 0 and ne > 0:
+            hn = min(int(n * _cfg_get(cfg, "HARD_BG_RATIO")), nh)
+            hard = randint(nh, hn)
+            easy = randint(ne, n - hn)
+            return [(1, hard), (2, easy)]
+        if nh > 0:
+            return [(1, randint(nh, n))]
+        return [(2, randint(ne, n))]
+
+    if nf > 0 and nb > 0:
+        n_fg = min(fg_per, nf)
+        parts = [(0, npr.permutation(nf)[:n_fg])] + bg(M - n_fg)
+    elif nf > 0:
+        parts = [(0, np.floor(npr.rand(M) * nf).astype(np.float32).astype(np.int64))]
+    elif nb > 0:
+        parts = bg(M)
+    else:
+        raise NotImplementedError(f"sample {sample}: FG={nf}, BG={nb}: no roi has a number for its maximum IoU")
+    out = np.concatenate([np.stack([np.full(len(pos), lid, np.int64), np.asarray(pos, np.int64)], 1) for lid, pos in parts])
+    if len(out) != M:   # a negative bg share (FG_RATIO above 1): the reference fails on the shape too
+        raise ValueError(f"sample {sample}: {len(out)} picks for ROI_PER_IMAGE = {M}")
+    return out.astype(np.int32)
+
+
+def _roi_args(rois, roi_scores, roi_labels, gt_boxes):
+    for t, name in ((rois, "rois"), (roi_scores, "roi_scores"), (roi_labels, "roi_labels"), (gt_boxes, "gt_boxes")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+    if rois.ndim != 3 or gt_boxes.ndim != 3 or roi_scores.shape != rois.shape[:2] or roi_labels.shape != rois.shape[:2] \
+            or gt_boxes.shape[0] != rois.shape[0] or gt_boxes.shape[2] != rois.shape[2] + 1:
+        raise ValueError(f"rois {tuple(rois.shape)}, roi_scores {tuple(roi_scores.shape)}, roi_labels "
+                         f"{tuple(roi_labels.shape)} and gt_boxes {tuple(gt_boxes.shape)} must be (B, N, 7 + C), (B, N), "
+                         f"(B, N) and (B, G, 7 + C + 1)")
+
+
+def roi_targets_limits(batch_size: int, cols: int, roi_per_image: int, n_rois: int = 0, n_gt: int = 0):
+    """the limits of the two calls, each a ValueError that names it; needs no device"""
+    if cols < 7 or cols > ROI_COLS_MAX:
+        raise ValueError(f"rois have {cols} columns: 7 + C, at most {ROI_COLS_MAX}")
+    if batch_size > ROI_BATCH_MAX:
+        raise ValueError(f"batch_size = {batch_size} is above the limit of {ROI_BATCH_MAX} samples per call")
+    if roi_per_image < 1:
+        raise ValueError(f"ROI_PER_IMAGE = {roi_per_image} is below the limit of 1")
+    if batch_size * max(n_rois, n_gt, roi_per_image) > 2 ** 31 - 1:
+        raise ValueError(f"{batch_size} samples of {n_rois} rois, {n_gt} gts and {roi_per_image} outputs are above the "
+                         f"limit of {2 ** 31 - 1} rows per call")
+
+
+def roi_targets_match(rois, roi_labels, gt_boxes, fg_thresh, bg_thresh_lo, reg_fg_thresh, by_class, workspace, counts_pinned):
+    """modest_roi_targets_match on PyTorch's current stream: BLOCKING (one synchronise).  rois (B, N, 7 + C) float32 and
+    roi_labels (B, N) int64 contiguous, gt_boxes (B, G, 7 + C + 1) float32 of any strides; workspace uint8 of
+    roi_targets_workspace_bytes(B, N); counts_pinned a pinned int32 tensor of at least 3 B words -> its (B, 3) view of
+    (fg, hard, easy) list lengths, valid on return"""
+    B, N, cols = (int(v) for v in rois.shape)
+    G = int(gt_boxes.shape[1])
+    _dev(rois, torch.float32, "rois"), _dev(roi_labels, torch.int64, "roi_labels"), _dev(workspace, torch.uint8, "workspace")
+    if gt_boxes.dtype != torch.float32 or not gt_boxes.is_cuda:
+        raise ValueError("gt_boxes must be a float32 device tensor")
+    if not counts_pinned.is_pinned() or counts_pinned.dtype != torch.int32 or counts_pinned.numel() < 3 * B:
+        raise ValueError("counts_pinned must be a pinned int32 tensor of at least 3 * B words")
+    with torch.cuda.device(rois.device):
+        check(load().modest_roi_targets_match(B, N, G, rois.data_ptr() if B * N else None, cols,
+                                              roi_labels.data_ptr() if B * N else None, gt_boxes.data_ptr() if B * G else None,
+                                              *(int(s) for s in gt_boxes.stride()), float(fg_thresh), float(bg_thresh_lo),
+                                              float(reg_fg_thresh), int(bool(by_class)), workspace.data_ptr(), workspace.numel(),
+                                              counts_pinned.data_ptr(), _stream()), "modest_roi_targets_match")
+    return counts_pinned[:3 * B].view(B, 3)
+
+
+def roi_targets_lists(workspace: torch.Tensor, batch_size: int, n_rois: int):
+    """test helper: what a match call left in `workspace` -> (counts (B, 3), max_iou (B, N) float32, assignment (B, N),
+    [fg, hard, easy] lists per sample) as numpy arrays; the byte offsets are the library's own
+    (modest_roi_targets_workspace_offsets)"""
+    B, N = int(batch_size), int(n_rois)
+    raw = workspace.cpu().numpy()
+    off = np.zeros(6, np.int64)
+    check(load().modest_roi_targets_workspace_offsets(B, N, off.ctypes.data), "modest_roi_targets_workspace_offsets")
+    counts = raw[off[0]:off[0] + 12 * B].view(np.int32).reshape(B, 3).copy()
+    iou = raw[off[1]:off[1] + 4 * B * N].view(np.float32).reshape(B, N).copy()
+    arr = [raw[off[k]:off[k] + 4 * B * N].view(np.int32).reshape(B, N) for k in (2, 3, 4, 5)]
+    lists = [[arr[1 + l][b, :counts[b, l]].copy() for l in range(3)] for b in range(B)]
+    return counts, iou, arr[0].copy(), lists
+
+
+def roi_targets_sample(picks, rois, roi_scores, roi_labels, gt_boxes, reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, score_type,
+                       workspace):
+    """modest_roi_targets_sample on PyTorch's current stream: enqueue only.  picks (B, M, 2) int32, pinned host or device
+    memory -> the eight outputs as a dict in the reference's key order.  A pinned table is read by the kernel through its
+    raw pointer, which PyTorch's host allocator does not see: the caller keeps it alive and unwritten until the stream has
+    passed this call (a freed pinned block can be handed out and overwritten before the kernel has read it).  A device
+    table is held by PyTorch's allocator in stream order and may be dropped at once."""
+    B, N, cols = (int(v) for v in rois.shape)
+    G, M = int(gt_boxes.shape[1]), int(picks.shape[1])
+    if picks.dtype != torch.int32 or picks.ndim != 3 or picks.shape[0] != B or picks.shape[2] != 2 or not picks.is_contiguous() \
+            or not (picks.is_cuda or picks.is_pinned()):
+        raise ValueError("picks must be a contiguous (B, M, 2) int32 tensor in pinned host or device memory")
+    if score_type not in ROI_SCORE_TYPES:
+        raise NotImplementedError(f"CLS_SCORE_TYPE {score_type!r}")
+    _dev(rois, torch.float32, "rois"), _dev(roi_scores, torch.float32, "roi_scores"), _dev(roi_labels, torch.int64, "roi_labels")
+    dev = rois.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+    out = {"rois": f(B, M, cols), "gt_of_rois": f(B, M, cols + 1), "gt_iou_of_rois": f(B, M), "roi_scores": f(B, M),
+           "roi_labels": i(B, M), "reg_valid_mask": i(B, M), "rcnn_cls_labels": i(B, M) if score_type == "cls" else f(B, M),
+           "gt_of_rois_src": f(B, M, cols + 1)}
+    den = float(cls_fg_thresh) - float(cls_bg_thresh)      # in double, rounded once by the float argument
+    with torch.cuda.device(dev):
+        check(load().modest_roi_targets_sample(B, N, G, M, picks.data_ptr(), rois.data_ptr() if B * N else None, cols,
+                                               roi_scores.data_ptr() if B * N else None,
+                                               roi_labels.data_ptr() if B * N else None,
+                                               gt_boxes.data_ptr() if B * G else None, *(int(s) for s in gt_boxes.stride()),
+                                               float(reg_fg_thresh), float(cls_fg_thresh), float(cls_bg_thresh), den,
+                                               ROI_SCORE_TYPES[score_type], workspace.data_ptr(), workspace.numel(),
+                                               out["rois"].data_ptr(), out["gt_of_rois"].data_ptr(),
+                                               out["gt_iou_of_rois"].data_ptr(), out["roi_scores"].data_ptr(),
+                                               out["roi_labels"].data_ptr(), out["reg_valid_mask"].data_ptr(),
+                                               out["rcnn_cls_labels"].data_ptr(), out["gt_of_rois_src"].data_ptr(), _stream()),
+              "modest_roi_targets_sample")
+    return out
+
+
+def roi_targets(rois: torch.Tensor, roi_scores: torch.Tensor, roi_labels: torch.Tensor, gt_boxes: torch.Tensor, cfg, *,
+                np_random=None, generator=None, workspace: Optional[torch.Tensor] = None,
+                counts_pinned: Optional[torch.Tensor] = None, picks_pinned: Optional[torch.Tensor] = None):
+    """RoIHeadTemplate.assign_targets of a batch on PyTorch's current stream: modest_roi_targets_match (one synchronise: the
+    list lengths reach the host), the reference's draws per sample from numpy's and torch's CPU generators (the global ones
+    when np_random / generator are None), modest_roi_targets_sample.  cfg: the TARGET_CONFIG (attributes or a dict).
+    rois (B, N, 7 + C), roi_scores (B, N), roi_labels (B, N), gt_boxes (B, G, 7 + C + 1, any strides): device tensors;
+    other floating types go through float32 and come back in rois' type.  -> the reference's dict of eight (B, M, .) tensors.
+    workspace (uint8, device), counts_pinned (int32, pinned, 3 B words) and picks_pinned (int32, pinned, 2 B M words) are
+    allocated when missing or too small.  Lifetime of picks_pinned: the sample kernel, which is only enqueued, reads the
+    caller's table where it lies, so the caller keeps it alive and unwritten until the stream has passed this call's work
+    (the next call here on the same stream may write it: its match call synchronises first); calls on several streams
+    need a table each.  Without one the picks go through a pinned block and a device copy that PyTorch's allocators hold
+    back by themselves, at the price of one small copy."""
+    _roi_args(rois, roi_scores, roi_labels, gt_boxes)
+    score_type = _cfg_get(cfg, "CLS_SCORE_TYPE")
+    if score_type not in ROI_SCORE_TYPES:
+        raise NotImplementedError(f"CLS_SCORE_TYPE {score_type!r}")
+    B, N, cols = (int(v) for v in rois.shape)
+    M = int(_cfg_get(cfg, "ROI_PER_IMAGE"))
+    roi_targets_limits(B, cols, M, N, int(gt_boxes.shape[1]))
+    dev, dtype = rois.device, rois.dtype
+    r32 = rois.float().contiguous()
+    s32 = roi_scores.float().contiguous()
+    lab = roi_labels.long().contiguous()
+    gt = gt_boxes if gt_boxes.dtype == torch.float32 else gt_boxes.float()
+    need = roi_targets_workspace_bytes(B, N)
+    if workspace is None or workspace.numel() < need or workspace.device != dev:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+    if counts_pinned is None or counts_pinned.numel() < 3 * B:
+        counts_pinned = torch.zeros((max(3 * B, 16),), dtype=torch.int32).pin_memory()
+    if picks_pinned is not None and picks_pinned.numel() < 2 * B * M:
+        picks_pinned = None
+    reg_fg, cls_fg = _cfg_get(cfg, "REG_FG_THRESH"), _cfg_get(cfg, "CLS_FG_THRESH")
+    counts = roi_targets_match(r32, lab, gt, min(reg_fg, cls_fg), _cfg_get(cfg, "CLS_BG_THRESH_LO"), reg_fg,
+                               _cfg_get(cfg, "SAMPLE_ROI_BY_EACH_CLASS", False), workspace, counts_pinned).numpy()
+    if picks_pinned is not None:
+        # the caller's table, read by the sample kernel where it lies.  It may be written here: the match call above has
+        # synchronised this stream, so the sample kernel of the call before on this stream has read it.  The caller keeps it
+        # alive until this call's work on the stream is complete.
+        staged = picks_pinned[:2 * B * M].view(B, M, 2)
+    else:
+        # a table of this call's own dies when the call returns, before the sample kernel need have started, and PyTorch's
+        # host allocator knows nothing of a kernel that reads a block through its raw pointer: it would hand the block to the
+        # next pin_memory().  So the kernel reads a device copy; the non-blocking copy records the event that holds the
+        # pinned block back until it has been read, and the device copy is freed in stream order.
+        staged = torch.empty((B, M, 2), dtype=torch.int32, pin_memory=True)
+    table = staged.numpy()
+    for b in range(B):
+        table[b] = roi_target_draws(counts[b], cfg, np_random, generator, sample=b)
+    picks = staged if picks_pinned is not None else staged.to(dev, non_blocking=True)
+    out = roi_targets_sample(picks, r32, s32, lab, gt, reg_fg, cls_fg, _cfg_get(cfg, "CLS_BG_THRESH"), score_type, workspace)
+    if dtype != torch.float32:
+        for k in ("rois", "gt_of_rois", "gt_iou_of_rois", "roi_scores", "gt_of_rois_src"):
+            out[k] = out[k].to(dtype)
+        if score_type == "roi_iou":
+            out["rcnn_cls_labels"] = out["rcnn_cls_labels"].to(dtype)
+    if roi_labels.dtype != torch.int64:
+        out["roi_labels"] = out["roi_labels"].to(roi_labels.dtype)
+    return out

@@ -39,6 +39,10 @@ so that the import finds the shims).  Where that module cannot be imported nothi
 two-stage detectors in one call -- on ``RoIHeadTemplate`` of
 ``pcdet.models.roi_heads.roi_head_template``, imported for it if it is not yet, after every other binding.  Where that
 module cannot be imported nothing is bound.
+
+``bind_roi_targets()``, a function of its own, sets ``modest_amd.utils.roi_targets.assign_targets`` -- the RoI target
+assignment of the two-stage heads in two calls -- on the same ``RoIHeadTemplate``; call it after
+``install``.  ``install`` itself is unchanged by it.
 """
 import importlib
 import importlib.util
@@ -68,6 +72,8 @@ POINT_TARGETS_NAME = "pcdet.models.dense_heads.point_head_template"
 POINT_TARGETS = "modest_amd.utils.point_head_targets"   # its method set on PointHeadTemplate by install(point_targets=True)
 PROPOSAL_LAYER_NAME = "pcdet.models.roi_heads.roi_head_template"
 PROPOSAL_LAYER = "modest_amd.utils.proposal_layer"   # its method set on RoIHeadTemplate by install(proposal_layer=True)
+ROI_TARGETS_NAME = PROPOSAL_LAYER_NAME
+ROI_TARGETS = "modest_amd.utils.roi_targets"         # its method set on RoIHeadTemplate by bind_roi_targets()
 
 
 class StandIn(types.ModuleType):
@@ -172,6 +178,24 @@ def _bind_proposal_layer():
     if head is None:
         return None
     importlib.import_module(PROPOSAL_LAYER).bind(head)
+    return mod
+
+
+def bind_roi_targets():
+    """RoIHeadTemplate.assign_targets := modest_amd.utils.roi_targets.assign_targets -- the RoI target assignment of the
+    two-stage heads -- in the reference's module if it is imported or can be -> that module, or
+    None.  A function of its own: install() and what it returns stay as they are.  Idempotent; before or after
+    ``import pcdet.models``; touches no GPU state."""
+    mod = sys.modules.get(ROI_TARGETS_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(ROI_TARGETS_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    head = getattr(mod, "RoIHeadTemplate", None)
+    if head is None:
+        return None
+    importlib.import_module(ROI_TARGETS).bind(head)
     return mod
 
 
