@@ -1254,6 +1254,53 @@ int modest_roi_targets_sample(int batch_size, int n_rois, int n_gt, int roi_per_
                               float *out_roi_scores_dev, int64_t *out_roi_labels_dev, int64_t *out_reg_valid_dev,
                               void *out_cls_labels_dev, float *out_gt_of_rois_src_dev, void *stream);
 
+/* ---- a33 post-processing (Detector3DTemplate.post_processing over class_agnostic_nms and generate_recall_record;
+ * DESIGN.md 7o) ------------------------------------------------------------------------------------------------------
+ * MULTI_CLASSES_NMS off.  The final boxes of a whole batch and its recall counters in one call: BLOCKING -- one stream
+ * synchronise at the end, no context, no device allocation; nothing is read back but the caller's pinned table, which the
+ * kernels write.  box, cls, batch_index, rows_per_sample and the two forms are those of modest_proposals.
+ *   score     the maximum over the class columns (the LOWEST column among equal maxima, a NaN above every number); with
+ *             normalized == 0 its sigmoid, (float)(1 / (1 + exp(-(double)x))), the double function rounded once;
+ *   threshold with has_score_thresh != 0 a row is a candidate iff score >= score_thresh (a NaN is none); with 0 every row
+ *             is, NaN scores first;
+ *   walk      the sample's min(pre_maxsize, candidates) highest scores -- equal scores (equal AFTER the sigmoid) in
+ *             ascending row order, -0 == +0 -- by the greedy NMS of modest_proposals, up to the post_maxsize-th survivor;
+ *   outputs   the n_b survivors of sample b in keep order at the front of row b of
+ *               pred_boxes (batch_size, post_maxsize, box_cols) float32, the rows of box bit for bit;
+ *               pred_scores (batch_size, post_maxsize) float32, the score, or with output_raw_score != 0 the maximum itself;
+ *               pred_labels (batch_size, post_maxsize) int64: column + 1, or labels_dev[row] where labels_dev
+ *                 (batch_size, rows_per_sample) int64 is given (dense form only);
+ *             rows n_b.. of the outputs are NOT written.
+ *   recall    with with_gt != 0.  gt (batch_size, n_gt, box_cols + 1) float32 by three strides counted in elements, trimmed
+ *             as modest_roi_targets_match trims (through the last row whose float32 sum in column order is not == 0, row 0
+ *             at the least; n_gt = 0: none).  Per valid gt the maximum over a list of boxes of the 3-D IoU iou(box, gt) of
+ *             modest_roi_targets_match, a NaN staying the maximum; the gt counts for threshold t iff maximum > t (a NaN
+ *             never, an empty list never).  The "rcnn" list: without rois (n_rois = -1) the sample's n_b final boxes; with
+ *             rois (batch_size, n_rois >= 0, roi_cols) float32 (dense form only) ALL rows of the sample, and a second
+ *             "roi" list, the sample's rois.
+ *   table     table_pinned_host (batch_size, 2 + 2 * n_thresh) int32 in pinned host memory the device can address, valid
+ *             when the call returns: n_b, valid gts, rcnn counts per threshold, roi counts per threshold (without gts the
+ *             words behind n_b are not written; without rois the roi counts are 0).  Per sample, no atomics on memory: the
+ *             caller adds the samples up.
+ * recall_thresh_host: n_thresh float32 in host memory, read before the call returns.
+ * Limits (the call fails and launches nothing): post_maxsize <= 1024, batch_size <= 65535, n_rows <= 2^31 - 1, box_cols,
+ * cls_cols and roi_cols <= 4096, n_thresh <= 16 (modest_post_process_max_thresholds), at most 2^31 - 1 gt and roi rows.
+ * n_gt, n_rois and the length of a list have no limit: a lane per gt, the list staged in LDS modest_post_process_tile()
+ * boxes at a time (a test builds its shapes around it).
+ * workspace 8-byte aligned, modest_post_process_workspace_bytes(n_rows, batch_size) bytes, need not be initialised.       */
+int modest_post_process_tile(void);
+int modest_post_process_max_thresholds(void);
+int64_t modest_post_process_workspace_bytes(int64_t n_rows, int batch_size);
+int modest_post_process(int64_t n_rows, int batch_size, int64_t rows_per_sample, const float *box_dev, int box_cols,
+                        const float *cls_dev, int cls_cols, const void *batch_index_dev, int batch_index_kind,
+                        int normalized, int has_score_thresh, float score_thresh, int output_raw_score,
+                        const int64_t *labels_dev, int pre_maxsize, int post_maxsize, float nms_thresh, int rotated,
+                        int with_gt, int n_gt, const float *gt_dev, int64_t gt_stride_b, int64_t gt_stride_n,
+                        int64_t gt_stride_c, int n_rois, const float *rois_dev, int roi_cols, int n_thresh,
+                        const float *recall_thresh_host, float *pred_boxes_dev, float *pred_scores_dev,
+                        int64_t *pred_labels_dev, int32_t *table_pinned_host, void *workspace_dev,
+                        int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

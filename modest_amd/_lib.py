@@ -155,6 +155,13 @@ SIGNATURES = {
     "modest_roi_targets_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, C.c_int64,
                                             C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, VP,
                                             C.c_int64, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "modest_post_process_tile": (C.c_int, []),
+    "modest_post_process_max_thresholds": (C.c_int, []),
+    "modest_post_process_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "modest_post_process": (C.c_int, [C.c_int64, C.c_int, C.c_int64, VP, C.c_int, VP, C.c_int, VP, C.c_int,
+                                      C.c_int, C.c_int, C.c_float, C.c_int, VP, C.c_int, C.c_int, C.c_float, C.c_int,
+                                      C.c_int, C.c_int, VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, VP, C.c_int, C.c_int,
+                                      VP, VP, VP, VP, VP, VP, C.c_int64, VP]),
 }
 
 _lib = None

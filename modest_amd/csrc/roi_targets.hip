@@ -23,6 +23,7 @@
 #include "common.h"
 #include "modest_hip.h"
 #include "iou_bev.h"
+#include "iou3d_steps.h"
 
 namespace {
 
@@ -72,10 +73,6 @@ struct MatchParams {
     int32_t *pinned;                   // (B, 3) host words
 };
 
-// torch.max / torch.min / torch.clamp(min=) of two numbers: a NaN propagates
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
-__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
-
 __global__ __launch_bounds__(RT_T) void rt_match(MatchParams p) {
     __shared__ PolyLds s_poly[RT_WAVES];
     __shared__ float s_gt[RT_TILE][RT_REC];
@@ -111,8 +108,7 @@ __global__ __launch_bounds__(RT_T) void rt_match(MatchParams p) {
             label = p.labels[(size_t)b * p.r + r];
         }
         const float4 ta = device_trig(a[6]);
-        const float a_top = a[2] + a[5] / 2, a_bot = a[2] - a[5] / 2;
-        const float va = a[3] * a[4] * a[5];
+        const Iou3dSide sa = iou3d_side(a);
         // (2) match
         float best = 0.f;
         int at = 0;
@@ -143,14 +139,7 @@ __global__ __launch_bounds__(RT_T) void rt_match(MatchParams p) {
 #pragma unroll
                     for (int q = 0; q < 7; ++q) bb[q] = s_gt[k][q];
                     const float4 tb = make_float4(s_gt[k][7], s_gt[k][8], s_gt[k][9], s_gt[k][10]);
-                    const float bev = box_overlap(a, bb, ta, tb, L);
-                    const float b_top = bb[2] + bb[5] / 2, b_bot = bb[2] - bb[5] / 2;
-                    const float d = min_nan(a_top, b_top) - max_nan(a_bot, b_bot);
-                    const float h = d < 0.f ? 0.f : d;           // clamp(min=0): a NaN stays
-                    const float o3 = bev * h;
-                    const float vb = bb[3] * bb[4] * bb[5];
-                    const float u = va + vb - o3;
-                    const float v = o3 / (u < 1e-6f ? 1e-6f : u);   // clamp(min=1e-6): a NaN stays
+                    const float v = iou3d_from_bev(sa, bb, box_overlap(a, bb, ta, tb, L));   // csrc/iou3d_steps.h
                     if (!any || v > best || (v != v && best == best)) {
                         best = v;
                         at = g0 + k;

@@ -1887,3 +1887,148 @@ def roi_targets(rois: torch.Tensor, roi_scores: torch.Tensor, roi_labels: torch.
     if roi_labels.dtype != torch.int64:
         out["roi_labels"] = out["roi_labels"].to(roi_labels.dtype)
     return out
+
+
+# --------------------------------------------------------------------------- post-processing
+POST_PROCESS_THRESH_MAX = 16                # len(RECALL_THRESH_LIST): modest_post_process_max_thresholds()
+
+
+def post_process_tile() -> int:
+    """boxes of a list a recall workgroup stages in LDS at a time"""
+    return int(load().modest_post_process_tile())
+
+
+def post_process_workspace_bytes(n_rows: int, batch_size: int) -> int:
+    nb = int(load().modest_post_process_workspace_bytes(int(n_rows), int(batch_size)))
+    if nb < 0:
+        check(nb, "modest_post_process_workspace_bytes")
+    return nb
+
+
+def post_process_table_words(batch_size: int, n_thresh: int) -> int:
+    """int32 words of the pinned table of a call: per sample its survivors, its valid gts, rcnn and roi counts per threshold"""
+    return int(batch_size) * (2 + 2 * int(n_thresh))
+
+
+def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int, pre_maxsize: int, post_maxsize: int,
+                 nms_thresh: float, *, rotated: bool = True, score_thresh: Optional[float] = None, normalized: bool = True,
+                 output_raw_score: bool = False, labels: Optional[torch.Tensor] = None,
+                 batch_index: Optional[torch.Tensor] = None, gt_boxes: Optional[torch.Tensor] = None,
+                 rois: Optional[torch.Tensor] = None, recall_thresh=(), workspace: Optional[torch.Tensor] = None,
+                 table: Optional[torch.Tensor] = None, out=None):
+    """modest_post_process on PyTorch's current stream: BLOCKING (one synchronise, inside the library).
+    box_preds / cls_preds / batch_index: the two forms of `proposals`, float32.  Per sample the rows whose score -- the class
+    maximum, its sigmoid (the double function rounded once) unless `normalized` -- is >= score_thresh (None: all rows) are
+    walked, the min(pre_maxsize, rows) highest first, by greedy NMS at nms_thresh up to the post_maxsize-th survivor.
+    labels: (B, N) int64 given labels (dense form), else the class column + 1.  gt_boxes (B, G, 7 + C + 1) float32 of any
+    strides switches the recall counters on; rois (B, R, 7 + C') float32 (dense form, needs gt_boxes) makes the "rcnn" list
+    all rows of the sample and adds the "roi" list.
+    -> (pred_boxes (B, post, 7 + C) float32, pred_scores (B, post) float32, pred_labels (B, post) int64, counts, recall):
+    padded buffers, freshly allocated (or the three tensors of `out`), of which sample b's first counts[b] rows are written
+    and the rest is not; counts a numpy (B,) int32 of the call's own; recall None without gt_boxes, else
+    {"gt": int, "rcnn": [int per threshold], "roi": [int per threshold]} summed over the samples.
+    workspace: uint8 device tensor of post_process_workspace_bytes(rows, B); table: pinned int32 tensor of
+    post_process_table_words(B, len(recall_thresh)); both allocated when missing or too small.  A table serves one stream
+    at a time: the kernels write it, and it is read here once the stream has been synchronised."""
+    for t, name in ((box_preds, "box_preds"), (cls_preds, "cls_preds")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    dev = box_preds.device
+    if cls_preds.device != dev:
+        raise ValueError("box_preds and cls_preds are on different devices")
+    B = int(batch_size)
+    if batch_index is None:
+        if box_preds.ndim != 3 or cls_preds.ndim != 3 or box_preds.shape[:2] != cls_preds.shape[:2] or box_preds.shape[0] != B:
+            raise ValueError(f"dense form: box_preds {tuple(box_preds.shape)} and cls_preds {tuple(cls_preds.shape)} must be "
+                             f"(batch_size = {B}, N, 7 + C) and (batch_size, N, K)")
+        per, kind, bidx = int(box_preds.shape[1]), 0, None
+    else:
+        if box_preds.ndim != 2 or cls_preds.ndim != 2 or box_preds.shape[0] != cls_preds.shape[0] \
+                or not torch.is_tensor(batch_index) or batch_index.numel() != box_preds.shape[0]:
+            raise ValueError(f"stacked form: box_preds {tuple(box_preds.shape)}, cls_preds {tuple(cls_preds.shape)} and "
+                             f"batch_index must be (N, 7 + C), (N, K) and (N)")
+        if labels is not None or rois is not None:
+            raise NotImplementedError("given labels or rois together with batch_index: no head produces that combination")
+        if batch_index.device != dev:
+            raise ValueError("batch_index is on another device than box_preds")
+        bidx = batch_index.reshape(-1)
+        if bidx.dtype not in _BATCH_INDEX_KINDS:
+            bidx = bidx.float() if bidx.dtype.is_floating_point else bidx.long()
+        bidx = bidx.contiguous()
+        per, kind = 0, _BATCH_INDEX_KINDS[bidx.dtype]
+    cols, K = int(box_preds.shape[-1]), int(cls_preds.shape[-1])
+    if cols < 7 or K < 1:
+        raise ValueError(f"box_preds needs 7 + C columns and cls_preds K >= 1, got {cols} and {K}")
+    box, cls = box_preds.contiguous(), cls_preds.contiguous()
+    n = int(box.numel() // cols)
+    P = int(post_maxsize)
+    if P < 0 or B < 0 or int(pre_maxsize) < 0:
+        raise ValueError("batch_size, pre_maxsize and post_maxsize must not be negative")
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.device != dev or labels.numel() != n:
+            raise ValueError(f"labels must be a device tensor of (batch_size, N) = ({B}, {per}) elements")
+        labels = labels.reshape(B, per).long().contiguous()
+    thr = np.ascontiguousarray(np.asarray(list(recall_thresh), dtype=np.float64).astype(np.float32))   # as torch compares
+    T = int(thr.size)
+    if T > POST_PROCESS_THRESH_MAX:
+        raise ValueError(f"RECALL_THRESH_LIST has {T} thresholds, above the limit of {POST_PROCESS_THRESH_MAX}")
+    G, R, rcols = 0, -1, 7
+    gt = None
+    if gt_boxes is not None:
+        if not torch.is_tensor(gt_boxes) or not gt_boxes.is_cuda or gt_boxes.dtype != torch.float32 or gt_boxes.device != dev:
+            raise ValueError("gt_boxes must be a float32 device tensor on the boxes' device")
+        if gt_boxes.ndim != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != cols + 1:
+            raise ValueError(f"gt_boxes {tuple(gt_boxes.shape)} must be (batch_size = {B}, G, 7 + C + 1 = {cols + 1})")
+        gt, G = gt_boxes, int(gt_boxes.shape[1])
+    if rois is not None:
+        if gt_boxes is None:
+            rois = None          # read by the recall counters only
+        else:
+            if not torch.is_tensor(rois) or not rois.is_cuda or rois.dtype != torch.float32 or rois.device != dev:
+                raise ValueError("rois must be a float32 device tensor on the boxes' device")
+            if rois.ndim != 3 or rois.shape[0] != B or rois.shape[2] < 7:
+                raise ValueError(f"rois {tuple(rois.shape)} must be (batch_size = {B}, R, 7 + C)")
+            rois = rois.contiguous()
+            R, rcols = int(rois.shape[1]), int(rois.shape[2])
+    want = (("pred_boxes", torch.float32, (B, P, cols)), ("pred_scores", torch.float32, (B, P)), ("pred_labels", torch.int64, (B, P)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
+    if len(out) != 3:
+        raise ValueError("out must be (pred_boxes, pred_scores, pred_labels)")
+    for t, (name, dtype, shape) in zip(out, want):
+        _dev(t, dtype, f"out {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.device != dev:
+            raise ValueError(f"out {name} is on {t.device}, box_preds on {dev}")
+    boxes, scores, labs = out
+    lib = load()
+    nbytes = post_process_workspace_bytes(n, B)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    stride = 2 + 2 * T
+    words = post_process_table_words(B, T)
+    if table is None or table.numel() < words:
+        table = torch.zeros((max(words, 16),), dtype=torch.int32).pin_memory()
+    if not table.is_pinned() or table.dtype != torch.int32 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous pinned int32 tensor")
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None      # noqa: E731
+    gs = tuple(int(s) for s in gt.stride()) if gt is not None else (0, 0, 0)
+    with torch.cuda.device(dev):
+        check(lib.modest_post_process(n, B, per, ptr(box), cols, ptr(cls), K, bidx.data_ptr() if bidx is not None else None, kind,
+                                      int(bool(normalized)), int(score_thresh is not None),
+                                      float(score_thresh) if score_thresh is not None else 0.0, int(bool(output_raw_score)),
+                                      labels.data_ptr() if labels is not None else None, int(pre_maxsize), P, float(nms_thresh),
+                                      int(bool(rotated)), int(gt is not None), G, ptr(gt), *gs, R, ptr(rois), rcols, T,
+                                      _np_ptr(thr) if T else None, ptr(boxes), ptr(scores), ptr(labs), table.data_ptr(),
+                                      workspace.data_ptr(), workspace.numel(), _stream()), "modest_post_process")
+    tab = table[:words].view(B, stride).numpy().copy() if B else np.zeros((0, stride), np.int32)
+    counts = np.ascontiguousarray(tab[:, 0]) if B else np.zeros((0,), np.int32)
+    recall = None
+    if gt is not None:
+        tot = tab[:, 1:].astype(np.int64).sum(0)
+        recall = {"gt": int(tot[0]), "rcnn": [int(v) for v in tot[1:1 + T]], "roi": [int(v) for v in tot[1 + T:1 + 2 * T]]}
+    return boxes, scores, labs, counts, recall

@@ -43,6 +43,11 @@ module cannot be imported nothing is bound.
 ``bind_roi_targets()``, a function of its own, sets ``modest_amd.utils.roi_targets.assign_targets`` -- the RoI target
 assignment of the two-stage heads in two calls -- on the same ``RoIHeadTemplate``; call it after
 ``install``.  ``install`` itself is unchanged by it.
+
+``bind_post_processing()``, a function of its own too, sets ``modest_amd.utils.post_processing.post_processing`` -- the
+test-time post-processing of every detector in one call -- on ``Detector3DTemplate`` of
+``pcdet.models.detectors.detector3d_template``, imported for it if it is not yet; a detector with an override of its own
+(``SECONDNetIoU``) keeps it.
 """
 import importlib
 import importlib.util
@@ -74,6 +79,8 @@ PROPOSAL_LAYER_NAME = "pcdet.models.roi_heads.roi_head_template"
 PROPOSAL_LAYER = "modest_amd.utils.proposal_layer"   # its method set on RoIHeadTemplate by install(proposal_layer=True)
 ROI_TARGETS_NAME = PROPOSAL_LAYER_NAME
 ROI_TARGETS = "modest_amd.utils.roi_targets"         # its method set on RoIHeadTemplate by bind_roi_targets()
+POST_PROCESSING_NAME = "pcdet.models.detectors.detector3d_template"
+POST_PROCESSING = "modest_amd.utils.post_processing"   # its method set on Detector3DTemplate by bind_post_processing()
 
 
 class StandIn(types.ModuleType):
@@ -196,6 +203,25 @@ def bind_roi_targets():
     if head is None:
         return None
     importlib.import_module(ROI_TARGETS).bind(head)
+    return mod
+
+
+def bind_post_processing():
+    """Detector3DTemplate.post_processing := modest_amd.utils.post_processing.post_processing -- the test-time
+    post-processing of the detectors -- in the reference's module if it is imported or can be -> that
+    module, or None.  A function of its own: install() and what it returns stay as they are.  Only the template's own
+    method is set, so a subclass that overrides it (SECONDNetIoU) keeps its own.  Idempotent; before or after
+    ``import pcdet.models``; touches no GPU state."""
+    mod = sys.modules.get(POST_PROCESSING_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(POST_PROCESSING_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    detector = getattr(mod, "Detector3DTemplate", None)
+    if detector is None:
+        return None
+    importlib.import_module(POST_PROCESSING).bind(detector)
     return mod
 
 
