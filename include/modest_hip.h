@@ -1301,6 +1301,46 @@ int modest_post_process(int64_t n_rows, int batch_size, int64_t rows_per_sample,
                         int64_t *pred_labels_dev, int32_t *table_pinned_host, void *workspace_dev,
                         int64_t workspace_bytes, void *stream);
 
+/* ---- a34 anchor-head loss with its gradients (AnchorHeadTemplate.get_loss over SigmoidFocalClassificationLoss,
+ * WeightedSmoothL1Loss / WeightedL1Loss and WeightedCrossEntropyLoss) ----------------------------------------
+ * The three losses of a whole batch and, where wanted, their gradients in one call: enqueue only -- no synchronise, no
+ * context, no device allocation, nothing read back.  All buffers are contiguous device memory, float32 unless said:
+ *   cls_preds (B, N, num_class), box_preds (B, N, code), dir_preds (B, N, bins) or NULL (no direction head),
+ *   labels (B, N) int32, or int64 with labels_int64 != 0: < 0 ignored, 0 background, c + 1 class c (with num_class == 1
+ *   every label > 0 is the one class; a label above num_class matches no class and is a positive of the box terms),
+ *   reg_targets (B, N, code), anchors (N, anchor_cols >= 7) NOT repeated over the batch, code_weights (code).
+ * Per sample cnt = the number of labels > 0 and w = 1.0f / max(cnt, 1); per anchor the classification weight is w where
+ * label >= 0 and the box / direction weight w where label > 0, else 0.
+ *   classification  t = 1 for the anchor's class column, s = sigmoid(x), aw = t alpha + (1 - t)(1 - alpha),
+ *                   pt = t (1 - s) + (1 - t) s, bce = max(x, 0) - x t + log1p(exp(-|x|)), value ((aw pt pt) bce) w;
+ *   box             positives only; column 6 is sin(p) cos(t) against cos(p) sin(t); a target that is NaN after that is
+ *                   replaced by the input; d = (in - tg) code_weight, n = |d|, value (n < beta ? 0.5 n n / beta :
+ *                   n - 0.5 beta) w, plain n w with beta < 1e-5;
+ *   direction       positives only; rot = tg[6] + anchor[6], v = rot - dir_offset, v - floor(v / 2pi) 2pi, the bin
+ *                   floor(. / (2pi / bins)) clamped to [0, bins - 1] (a NaN: bin 0); value -log_softmax(logits)[bin] w.
+ * float32 in this order, one rounding per operation, Python's scalars (beta, dir_offset, the weights, 2pi, 2pi / bins,
+ * 0.5 beta) rounded to float32 first; exp, log, log1p, sin, cos and the sigmoid are the double function rounded once.
+ * losses (4): cls = (sum / B) cls_weight, loc, dir likewise (0 without a direction head), rpn = cls + (loc + dir).  The
+ * sums run over a fixed tree: no float atomics, the same bits at every run.
+ * grad_cls / grad_box / grad_dir: all NULL (no gradients), or buffers of the predictions' shapes (grad_dir NULL without a
+ * direction head) that receive d rpn / d prediction -- the loss weights and 1 / B inside -- as autograd's chain through the
+ * expressions above gives it (at a logit of +-0 the bce derivative is 1 - t); EVERY element is written, the rows of anchors
+ * that are not positive with zeros.
+ * Limits (the call fails and launches nothing): 1 <= batch_size <= 65535, num_class <= 32, 7 <= code <= 16, bins <= 8,
+ * gamma == 2, n_anchors < 2^39.  workspace 4-byte aligned, modest_anchor_loss_workspace_bytes(batch_size, n_anchors) bytes,
+ * need not be initialised.
+ * modest_anchor_loss_backward multiplies the three gradient buffers (n_cls, n_box, n_dir elements; n_dir = 0 without a
+ * direction head) in place by the float32 upstream gradient at upstream_dev, one rounding per element: enqueue only.          */
+int64_t modest_anchor_loss_workspace_bytes(int batch_size, int64_t n_anchors);
+int modest_anchor_loss(int batch_size, int64_t n_anchors, int num_class, int code, int bins, const float *cls_preds_dev,
+                       const float *box_preds_dev, const float *dir_preds_dev, const void *labels_dev, int labels_int64,
+                       const float *reg_targets_dev, const float *anchors_dev, int anchor_cols,
+                       const float *code_weights_dev, float beta, float dir_offset, float cls_weight, float loc_weight,
+                       float dir_weight, float alpha, float gamma, float *losses_dev, float *grad_cls_dev,
+                       float *grad_box_dev, float *grad_dir_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_anchor_loss_backward(int64_t n_cls, int64_t n_box, int64_t n_dir, float *grad_cls_dev, float *grad_box_dev,
+                                float *grad_dir_dev, const float *upstream_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

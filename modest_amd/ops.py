@@ -2032,3 +2032,121 @@ def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: i
         tot = tab[:, 1:].astype(np.int64).sum(0)
         recall = {"gt": int(tot[0]), "rcnn": [int(v) for v in tot[1:1 + T]], "roi": [int(v) for v in tot[1 + T:1 + 2 * T]]}
     return boxes, scores, labs, counts, recall
+
+
+# --------------------------------------------------------------------------- anchor-head loss
+ANCHOR_LOSS_MAX_CLASS = 32      # class columns of an anchor
+ANCHOR_LOSS_MAX_CODE = 16       # box code columns
+ANCHOR_LOSS_MAX_BINS = 8        # NUM_DIR_BINS
+ANCHOR_LOSS_MAX_BATCH = 65535   # samples per call: the grid's second dimension
+
+
+def anchor_loss_workspace_bytes(batch_size: int, n_anchors: int) -> int:
+    nb = int(load().modest_anchor_loss_workspace_bytes(int(batch_size), int(n_anchors)))
+    if nb < 0:
+        check(nb, "modest_anchor_loss_workspace_bytes")
+    return nb
+
+
+def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Optional[torch.Tensor], labels: torch.Tensor,
+                reg_targets: torch.Tensor, anchors: torch.Tensor, code_weights: torch.Tensor, *, beta: float = 1.0 / 9.0,
+                dir_offset: float = 0.0, cls_weight: float = 1.0, loc_weight: float = 1.0, dir_weight: float = 1.0,
+                alpha: float = 0.25, gamma: float = 2.0, want_grad: bool = True, workspace: Optional[torch.Tensor] = None,
+                out=None):
+    """modest_anchor_loss on PyTorch's current stream: enqueue only, nothing is read back.
+    cls_preds (B, N, C), box_preds (B, N, code), dir_preds (B, N, bins) or None: float32 device tensors, made contiguous when
+    they are not; labels (B, N) int32 or int64; reg_targets (B, N, code), anchors (N, >= 7), code_weights (code): float32,
+    contiguous.  The scalars are rounded to float32, as torch rounds a Python scalar that meets a float32 tensor.
+    -> (losses (4) float32 [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss], grads): grads is None without want_grad, else
+    (grad_cls, grad_box, grad_dir or None) of the predictions' shapes, d rpn_loss / d prediction, every element written.
+    `out` = (losses, grad_cls, grad_box, grad_dir) supplies the buffers (the gradients None without want_grad)."""
+    for t, name in ((cls_preds, "cls_preds"), (box_preds, "box_preds"), (dir_preds, "dir_preds"), (labels, "labels"),
+                    (reg_targets, "reg_targets"), (anchors, "anchors"), (code_weights, "code_weights")):
+        if t is None and name == "dir_preds":
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if name == "labels":
+            if t.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"labels must be int32 or int64, got {t.dtype}")
+        elif t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    dev = cls_preds.device
+    if cls_preds.ndim != 3 or box_preds.ndim != 3 or cls_preds.shape[:2] != box_preds.shape[:2]:
+        raise ValueError(f"cls_preds {tuple(cls_preds.shape)} and box_preds {tuple(box_preds.shape)} must be (B, N, C) and (B, N, code)")
+    B, N, K = (int(v) for v in cls_preds.shape)
+    code = int(box_preds.shape[2])
+    bins = 0
+    if dir_preds is not None:
+        if dir_preds.ndim != 3 or tuple(dir_preds.shape[:2]) != (B, N):
+            raise ValueError(f"dir_preds {tuple(dir_preds.shape)} must be (B, N, bins) = ({B}, {N}, bins)")
+        bins = int(dir_preds.shape[2])
+    if tuple(labels.shape) != (B, N) or tuple(reg_targets.shape) != (B, N, code):
+        raise ValueError(f"labels {tuple(labels.shape)} and reg_targets {tuple(reg_targets.shape)} must be ({B}, {N}) and ({B}, {N}, {code})")
+    if anchors.ndim != 2 or anchors.shape[0] != N or anchors.shape[1] < 7:
+        raise ValueError(f"anchors {tuple(anchors.shape)} must be (N, >= 7) = ({N}, >= 7), not repeated over the batch")
+    if tuple(code_weights.shape) != (code,):
+        raise ValueError(f"code_weights {tuple(code_weights.shape)} must be (code,) = ({code},)")
+    if K < 1 or K > ANCHOR_LOSS_MAX_CLASS:
+        raise ValueError(f"num_class = {K} is outside the limit of 1 .. {ANCHOR_LOSS_MAX_CLASS} class columns")
+    if code < 7 or code > ANCHOR_LOSS_MAX_CODE:
+        raise ValueError(f"code size = {code} is outside the limit of 7 .. {ANCHOR_LOSS_MAX_CODE} box columns")
+    if dir_preds is not None and (bins < 1 or bins > ANCHOR_LOSS_MAX_BINS):
+        raise ValueError(f"NUM_DIR_BINS = {bins} is outside the limit of 1 .. {ANCHOR_LOSS_MAX_BINS} direction bins")
+    if B < 1 or B > ANCHOR_LOSS_MAX_BATCH:
+        raise ValueError(f"batch_size = {B} is outside the limit of 1 .. {ANCHOR_LOSS_MAX_BATCH} samples per call")
+    if float(gamma) != 2.0:
+        raise ValueError(f"gamma = {gamma}: only gamma = 2 is provided (the focal power is the product pt * pt)")
+    for t, name in ((labels, "labels"), (reg_targets, "reg_targets"), (anchors, "anchors"), (code_weights, "code_weights")):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, cls_preds on {dev}")
+    cls, box = cls_preds.contiguous(), box_preds.contiguous()
+    dirp = dir_preds.contiguous() if dir_preds is not None else None
+    want = (("losses", (4,)), ("grad_cls", (B, N, K)), ("grad_box", (B, N, code)), ("grad_dir", (B, N, bins)))
+    if out is None:
+        out = [torch.empty(shape, dtype=torch.float32, device=dev) if (i == 0 or (want_grad and (i < 3 or dirp is not None))) else None
+               for i, (_, shape) in enumerate(want)]
+    if len(out) != 4:
+        raise ValueError("out must be (losses, grad_cls, grad_box, grad_dir)")
+    for i, (t, (name, shape)) in enumerate(zip(out, want)):
+        need = i == 0 or (want_grad and (i < 3 or dirp is not None))
+        if (t is not None) != need:
+            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
+        if t is not None:
+            _dev(t, torch.float32, f"out {name}")
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
+    losses, gcls, gbox, gdir = out
+    nbytes = anchor_loss_workspace_bytes(B, N)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        check(load().modest_anchor_loss(B, N, K, code, bins, ptr(cls), ptr(box), ptr(dirp), ptr(labels),
+                                        int(labels.dtype == torch.int64), ptr(reg_targets), ptr(anchors), int(anchors.shape[1]),
+                                        ptr(code_weights), float(beta), float(dir_offset), float(cls_weight), float(loc_weight),
+                                        float(dir_weight), float(alpha), float(gamma), ptr(losses), ptr(gcls), ptr(gbox),
+                                        ptr(gdir), workspace.data_ptr(), workspace.numel(), _stream()), "modest_anchor_loss")
+    return losses, ((gcls, gbox, gdir) if want_grad else None)
+
+
+def anchor_loss_backward(grads, upstream: torch.Tensor):
+    """modest_anchor_loss_backward on PyTorch's current stream: the gradient buffers of `anchor_loss` (grad_dir may be None)
+    times the float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
+    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("upstream must be a float32 device tensor of one element")
+    live = [g for g in grads if g is not None]
+    for g in live:
+        _dev(g, torch.float32, "a gradient buffer")
+        if g.device != upstream.device:
+            raise ValueError("the gradient buffers and upstream are on different devices")
+    gcls, gbox, gdir = grads
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    num = lambda t: int(t.numel()) if t is not None else 0       # noqa: E731
+    with torch.cuda.device(upstream.device):
+        check(load().modest_anchor_loss_backward(num(gcls), num(gbox), num(gdir), ptr(gcls), ptr(gbox), ptr(gdir),
+                                                 upstream.data_ptr(), _stream()), "modest_anchor_loss_backward")
+    return grads

@@ -1,0 +1,198 @@
+"""Drop-in for ``AnchorHeadTemplate.get_loss`` of OpenPCDet's anchor heads
+(``pcdet/models/dense_heads/anchor_head_template.py``, over ``SigmoidFocalClassificationLoss``, ``WeightedSmoothL1Loss`` /
+``WeightedL1Loss`` and ``WeightedCrossEntropyLoss`` of ``pcdet/utils/loss_utils.py``) on the GPU:
+what closes every training step of PointPillars, SECOND, PV-RCNN, Voxel R-CNN and PartA2.
+
+One library call (``modest_amd.ops.anchor_loss``, csrc/anchor_loss.hip) on PyTorch's current stream computes the three losses
+and, where a prediction requires a gradient, the three gradients of ``rpn_loss`` in the same pass: no one-hot tensor, no
+repeated anchors, no concatenated box tensors, nothing kept for autograd but the three gradient buffers.  ``backward`` is one
+more library call, which scales those buffers in place by the upstream gradient read from the device.  ``tb_dict``'s floats
+are read through a small pinned table after ONE stream synchronise (the reference waits four times).  The flattened anchors,
+the workspace and the pinned table are kept on the head.
+
+Provided: a single head (``USE_MULTIHEAD: False``), the reference's three loss classes (the focal loss with alpha = 0.25 and
+gamma = 2), float32 predictions.  ``USE_MULTIHEAD: True``, another ``cls_loss_func`` / ``reg_loss_func`` / ``dir_loss_func`` and
+predictions of another type raise ``NotImplementedError`` naming the option; the limits (``ValueError``): ``num_class`` <= 32,
+code size <= 16, ``NUM_DIR_BINS`` <= 8, batch <= 65535.  A head whose class overrides ``get_cls_layer_loss`` or
+``get_box_reg_layer_loss`` (``AnchorHeadMulti``) is handed to the method this one replaced.
+
+One visible difference: with ``num_class == 1`` the reference overwrites the positive labels in
+``forward_ret_dict['box_cls_labels']`` with 1; this method leaves the dict as it found it.
+
+``bind(cls)`` sets the method on a head class; ``pcdet_bind.bind_anchor_loss()`` does that for the reference's
+``AnchorHeadTemplate``.
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+CLS_LOSS = "SigmoidFocalClassificationLoss"
+REG_LOSSES = ("WeightedSmoothL1Loss", "WeightedL1Loss")
+DIR_LOSS = "WeightedCrossEntropyLoss"
+PARTS = ("get_cls_layer_loss", "get_box_reg_layer_loss")   # an override of either: the head computes another loss
+
+_ORIGINAL = {}   # class -> the get_loss that bind() replaced on it (None: it had none of its own)
+
+
+def _get(cfg, name, *default):
+    if isinstance(cfg, dict):
+        return cfg.get(name, *default) if default else cfg[name]
+    return getattr(cfg, name, *default)
+
+
+class AnchorLossFunction(torch.autograd.Function):
+    """(cls_preds, box_preds, dir_preds or None, labels, reg_targets, anchors, code_weights, scalars, workspace) -> losses (4):
+    [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss].  Only element 3, rpn_loss, carries a gradient: backward scales the
+    unit gradients kept by forward with the upstream gradient of that element, in place, so it runs once."""
+
+    @staticmethod
+    def forward(ctx, cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, code_weights, scalars, workspace):
+        from .. import ops
+        losses, grads = ops.anchor_loss(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, code_weights,
+                                        want_grad=True, workspace=workspace, **scalars)
+        ctx.unit_grads = grads
+        ctx.shapes = (cls_preds.shape, box_preds.shape, None if dir_preds is None else dir_preds.shape)
+        return losses
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_losses):
+        from .. import ops
+        grads = ctx.unit_grads
+        if grads is None:
+            raise RuntimeError("the anchor loss was differentiated a second time: its gradient buffers were scaled in place")
+        ctx.unit_grads = None
+        upstream = grad_losses.contiguous()[3:4]
+        if upstream.dtype != torch.float32:
+            upstream = upstream.float()
+        ops.anchor_loss_backward(grads, upstream)
+        out = tuple(None if g is None else g.view(s) for g, s in zip(grads, ctx.shapes))
+        return out + (None,) * 6
+
+
+def _flat_anchors(head):
+    """(N, cols) anchors of a single head on the device, flattened as the reference flattens them, built once per list of
+    anchor tensors (keyed as modest_amd.utils.target_assigner keys its tables)"""
+    anchors = head.anchors
+    given = list(anchors) if isinstance(anchors, (list, tuple)) else [anchors]
+    key = getattr(head, "_modest_anchor_loss_key", None)
+    if key is not None and len(key) == len(given) and all(a is b and a._version == v for a, (b, v) in zip(given, key)):
+        return head._modest_anchor_loss_anchors
+    if isinstance(anchors, (list, tuple)):
+        flat = torch.cat(given, dim=-3) if len(given) > 1 else given[0]
+    else:
+        flat = anchors
+    flat = flat.reshape(-1, flat.shape[-1]).float().contiguous()
+    head._modest_anchor_loss_anchors = flat
+    head._modest_anchor_loss_key = [(a, a._version) for a in given]
+    return flat
+
+
+def _buffers(head, dev, B, N):
+    """the workspace and the pinned table kept on `head`; a table serves one stream at a time"""
+    from .. import ops
+    need = ops.anchor_loss_workspace_bytes(B, N)
+    ws = getattr(head, "_modest_anchor_loss_workspace", None)
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = head._modest_anchor_loss_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+    table = getattr(head, "_modest_anchor_loss_table", None)
+    if table is None:
+        table = head._modest_anchor_loss_table = torch.zeros((4,), dtype=torch.float32).pin_memory()
+    return ws, table
+
+
+def _bound_class(head_type):
+    for c in head_type.__mro__:
+        if c in _ORIGINAL:
+            return c
+    return None
+
+
+def get_loss(self):
+    """-> (rpn_loss, tb_dict): rpn_loss a 0-dim device tensor with its gradient function, tb_dict the Python floats
+    rpn_loss_cls, rpn_loss_loc, rpn_loss_dir (only with a direction head) and rpn_loss"""
+    from .. import ops
+    base = _bound_class(type(self))
+    if base is not None and any(getattr(type(self), part, None) is not getattr(base, part, None) for part in PARTS):
+        original = _ORIGINAL[base]
+        if original is None:
+            original = next(c.__dict__["get_loss"] for c in base.__mro__[1:] if "get_loss" in c.__dict__)
+        return original(self)
+    model_cfg = self.model_cfg
+    if _get(model_cfg, "USE_MULTIHEAD", False) or getattr(self, "use_multihead", False):
+        raise NotImplementedError("USE_MULTIHEAD: True is not provided by modest_amd's anchor loss")
+    cls_fn, reg_fn, dir_fn = self.cls_loss_func, self.reg_loss_func, self.dir_loss_func
+    if type(cls_fn).__name__ != CLS_LOSS:
+        raise NotImplementedError(f"cls_loss_func = {type(cls_fn).__name__} is not provided: {CLS_LOSS} only")
+    alpha, gamma = float(getattr(cls_fn, "alpha", 0.25)), float(getattr(cls_fn, "gamma", 2.0))
+    if alpha != 0.25 or gamma != 2.0:
+        raise NotImplementedError(f"cls_loss_func with alpha = {alpha}, gamma = {gamma} is not provided: alpha = 0.25, gamma = 2.0 only")
+    if type(reg_fn).__name__ not in REG_LOSSES:
+        raise NotImplementedError(f"reg_loss_func = {type(reg_fn).__name__} (REG_LOSS_TYPE) is not provided: one of {REG_LOSSES}")
+    ret = self.forward_ret_dict
+    cls_preds, box_preds = ret['cls_preds'], ret['box_preds']
+    dir_preds = ret.get('dir_cls_preds', None)
+    if dir_preds is not None and type(dir_fn).__name__ != DIR_LOSS:
+        raise NotImplementedError(f"dir_loss_func = {type(dir_fn).__name__} is not provided: {DIR_LOSS} only")
+    for t, name in ((cls_preds, "cls_preds"), (box_preds, "box_preds"), (dir_preds, "dir_cls_preds")):
+        if t is not None and t.dtype != torch.float32:
+            raise NotImplementedError(f"{name} of {t.dtype} (mixed precision) is not provided: float32 predictions only")
+    labels, targets = ret['box_cls_labels'], ret['box_reg_targets']
+    loss_cfg = _get(model_cfg, "LOSS_CONFIG")
+    weights = _get(loss_cfg, "LOSS_WEIGHTS")
+    batch_size = int(cls_preds.shape[0])
+    num_class = int(self.num_class)
+    cls = cls_preds.reshape(batch_size, -1, num_class)
+    box = box_preds.reshape(batch_size, -1, box_preds.shape[-1] // int(self.num_anchors_per_location))
+    N, code = int(box.shape[1]), int(box.shape[2])
+    bins = 0
+    dirp = None
+    if dir_preds is not None:
+        bins = int(_get(model_cfg, "NUM_DIR_BINS"))
+        dirp = dir_preds.reshape(batch_size, -1, bins)
+    for value, limit, name in ((num_class, ops.ANCHOR_LOSS_MAX_CLASS, "num_class"), (code, ops.ANCHOR_LOSS_MAX_CODE, "code size"),
+                               (bins, ops.ANCHOR_LOSS_MAX_BINS, "NUM_DIR_BINS"), (batch_size, ops.ANCHOR_LOSS_MAX_BATCH, "batch_size")):
+        if value > limit:
+            raise ValueError(f"{name} = {value} is above the limit of {limit}")
+    for t, name in ((cls_preds, "cls_preds"), (box_preds, "box_preds"), (dir_preds, "dir_cls_preds"),
+                    (labels, "box_cls_labels"), (targets, "box_reg_targets")):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda):
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+    if labels.dtype not in (torch.int32, torch.int64):
+        labels = labels.long()
+    labels = labels.reshape(batch_size, -1).contiguous()
+    targets = targets.float().reshape(batch_size, -1, targets.shape[-1]).contiguous()
+    anchors = _flat_anchors(self)
+    code_weights = getattr(reg_fn, "code_weights", None)
+    if code_weights is None:
+        code_weights = torch.ones((code,), dtype=torch.float32, device=cls.device)
+    elif not torch.is_tensor(code_weights):
+        code_weights = torch.tensor([float(v) for v in code_weights], dtype=torch.float32, device=cls.device)
+    else:
+        code_weights = code_weights.to(device=cls.device, dtype=torch.float32).reshape(-1).contiguous()
+    scalars = dict(beta=float(getattr(reg_fn, "beta", 0.0)), dir_offset=float(_get(model_cfg, "DIR_OFFSET", 0.0)) if dirp is not None else 0.0,
+                   cls_weight=float(weights['cls_weight']), loc_weight=float(weights['loc_weight']),
+                   dir_weight=float(weights['dir_weight']) if dirp is not None else 0.0, alpha=alpha, gamma=gamma)
+    ws, table = _buffers(self, cls.device, batch_size, N)
+    wants = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (cls, box, dirp))
+    if wants:
+        losses = AnchorLossFunction.apply(cls, box, dirp, labels, targets, anchors, code_weights, scalars, ws)
+    else:
+        losses, _ = ops.anchor_loss(cls, box, dirp, labels, targets, anchors, code_weights, want_grad=False, workspace=ws, **scalars)
+    table.copy_(losses.detach(), non_blocking=True)
+    torch.cuda.current_stream(cls.device).synchronize()      # the one host wait
+    values = table.tolist()
+    tb_dict = {'rpn_loss_cls': values[0], 'rpn_loss_loc': values[1]}
+    if dirp is not None:
+        tb_dict['rpn_loss_dir'] = values[2]
+    tb_dict['rpn_loss'] = values[3]
+    return losses[3], tb_dict
+
+
+def bind(cls):
+    """set get_loss on a head class (AnchorHeadTemplate or a subclass) -> cls; the method it had is kept for the heads
+    that override a part of the loss.  Idempotent."""
+    if cls.__dict__.get("get_loss") is get_loss:
+        return cls
+    _ORIGINAL[cls] = cls.__dict__.get("get_loss")
+    cls.get_loss = get_loss
+    return cls

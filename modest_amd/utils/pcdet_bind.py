@@ -48,6 +48,11 @@ assignment of the two-stage heads in two calls -- on the 
 test-time post-processing of every detector in one call -- on ``Detector3DTemplate`` of
 ``pcdet.models.detectors.detector3d_template``, imported for it if it is not yet; a detector with an override of its own
 (``SECONDNetIoU``) keeps it.
+
+``bind_anchor_loss()``, a function of its own as well, sets ``modest_amd.utils.anchor_head_loss.get_loss`` -- the loss of
+the anchor heads with its gradients in one call -- on ``AnchorHeadTemplate`` of
+``pcdet.models.dense_heads.anchor_head_template``, imported for it if it is not yet; a head that overrides a part of the
+loss (``AnchorHeadMulti``) reaches the method that was replaced.
 """
 import importlib
 import importlib.util
@@ -81,6 +86,8 @@ ROI_TARGETS_NAME = PROPOSAL_LAYER_NAME
 ROI_TARGETS = "modest_amd.utils.roi_targets"         # its method set on RoIHeadTemplate by bind_roi_targets()
 POST_PROCESSING_NAME = "pcdet.models.detectors.detector3d_template"
 POST_PROCESSING = "modest_amd.utils.post_processing"   # its method set on Detector3DTemplate by bind_post_processing()
+ANCHOR_LOSS_NAME = "pcdet.models.dense_heads.anchor_head_template"
+ANCHOR_LOSS = "modest_amd.utils.anchor_head_loss"      # its method set on AnchorHeadTemplate by bind_anchor_loss()
 
 
 class StandIn(types.ModuleType):
@@ -222,6 +229,25 @@ def bind_post_processing():
     if detector is None:
         return None
     importlib.import_module(POST_PROCESSING).bind(detector)
+    return mod
+
+
+def bind_anchor_loss():
+    """AnchorHeadTemplate.get_loss := modest_amd.utils.anchor_head_loss.get_loss -- the loss of the anchor heads with its
+    gradients -- in the reference's module if it is imported or can be -> that module, or None.  A
+    function of its own: install() and what it returns stay as they are.  Only the template's own method is set, and the
+    one it had is kept: a head that overrides get_cls_layer_loss or get_box_reg_layer_loss (AnchorHeadMulti) is handed to
+    it.  Idempotent; before or after ``import pcdet.models``; touches no GPU state."""
+    mod = sys.modules.get(ANCHOR_LOSS_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(ANCHOR_LOSS_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    head = getattr(mod, "AnchorHeadTemplate", None)
+    if head is None:
+        return None
+    importlib.import_module(ANCHOR_LOSS).bind(head)
     return mod
 
 
