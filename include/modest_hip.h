@@ -1341,6 +1341,51 @@ int modest_anchor_loss(int batch_size, int64_t n_anchors, int num_class, int cod
 int modest_anchor_loss_backward(int64_t n_cls, int64_t n_box, int64_t n_dir, float *grad_cls_dev, float *grad_box_dev,
                                 float *grad_dir_dev, const float *upstream_dev, void *stream);
 
+/* ---- a35 RoI-head loss with its gradients (RoIHeadTemplate.get_loss over BinaryCrossEntropy, ResidualCoder,
+ * WeightedSmoothL1Loss and get_corner_loss_lidar) ------------------------------------------------------------
+ * The losses of all R = B x ROI_PER_IMAGE rows and, where wanted, their gradients in one call: enqueue only -- no
+ * synchronise, no context, no device allocation, nothing read back.  Device memory, float32 and contiguous unless said:
+ *   rcnn_cls (R) logits, rcnn_reg (R, code),
+ *   cls_labels (R) int32 (label_kind 0), int64 (1) or float32 (2): a row counts iff label >= 0, t = float(label),
+ *   reg_valid_mask (R) int32, or int64 with mask_int64 != 0: a row is foreground iff mask > 0,
+ *   gt_of_rois (R, >= code) in the roi's canonical frame and gt_of_rois_src (R, >= code) in the scene's, each read through
+ *   its row stride (in elements); rois (R, code); code_weights (code).
+ * With fg = the foreground rows and valid = the counted rows:
+ *   classification  s = sigmoid(x), (t - 1) max(log1p(-s), -100) - t max(log(s), -100) over the counted rows,
+ *                   rcnn_loss_cls = (sum / max(valid, 1)) cls_weight;
+ *   regression      foreground rows; the target is ResidualCoder.encode_torch of gt_of_rois against the roi with centre and
+ *                   heading zeroed, both sets of sizes clamped at 1e-5; a NaN target is replaced by the input;
+ *                   d = (in - tg) code_weight, n = |d|, value n < beta ? 0.5 n n / beta : n - 0.5 beta (plain n with
+ *                   beta < 1e-5), summed over the columns in order; rcnn_loss_reg = (sum / max(fg, 1)) reg_weight;
+ *   corner          with corner != 0 and fg > 0, foreground rows: rcnn_reg decoded against the roi with zero centre (sizes
+ *                   NOT clamped), its centre rotated by the roi's heading and moved to the roi's centre; the 8 corners of
+ *                   that box, of gt_of_rois_src[0:7] and of that gt with heading + float32(pi); per corner the smaller of
+ *                   the two distances sqrt((dx dx + dy dy) + dz dz) through smooth L1 with beta 1; the mean of the 8, the
+ *                   mean over fg, times corner_weight;
+ *   rcnn_loss       cls + (reg + corner), or cls + reg without the corner term.
+ * float32 in the order DESIGN.md 7q writes down, one rounding per operation, Python's scalars rounded to float32 first; exp,
+ * log, log1p, sin, cos and the sigmoid are the double function rounded once; sqrt and / are correctly rounded.  The sums run
+ * over the fixed tree of 7p: no float atomics, the same bits at every run.  A row that is not counted / not foreground is
+ * not read for that term (a non-finite value there poisons the reference's sum; it does not reach ours).
+ * table (6): rcnn_loss_cls, rcnn_loss_reg (the smooth-L1 part alone), rcnn_loss_corner (0 without), rcnn_loss, fg, valid.
+ * grad_cls (R) / grad_reg (R, code): both NULL (no gradients), or buffers that receive d rcnn_loss / d prediction as
+ * autograd's chain through the expressions above gives it (min of two equal distances hands half to each side, the norm
+ * of a zero vector hands on 0, columns >= 7 get nothing from the corner term); EVERY element is written.
+ * Limits (the call fails and launches nothing): n_rows <= modest_roi_loss_max_rows() = 2^20, 7 <= code <= 16, the row
+ * strides >= code.  workspace 4-byte aligned, modest_roi_loss_workspace_bytes(n_rows) bytes, need not be initialised.
+ * modest_roi_loss_backward multiplies the two gradient buffers (n_cls, n_reg elements) in place by the float32 upstream
+ * gradient at upstream_dev, one rounding per element: enqueue only.                                                          */
+int64_t modest_roi_loss_max_rows(void);
+int64_t modest_roi_loss_workspace_bytes(int64_t n_rows);
+int modest_roi_loss(int64_t n_rows, int code, const float *rcnn_cls_dev, const float *rcnn_reg_dev,
+                    const void *cls_labels_dev, int label_kind, const void *reg_valid_mask_dev, int mask_int64,
+                    const float *gt_of_rois_dev, int64_t gt_row_stride, const float *gt_of_rois_src_dev,
+                    int64_t src_row_stride, const float *rois_dev, const float *code_weights_dev, float beta,
+                    float cls_weight, float reg_weight, float corner_weight, int corner, float *table_dev,
+                    float *grad_cls_dev, float *grad_reg_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_roi_loss_backward(int64_t n_cls, int64_t n_reg, float *grad_cls_dev, float *grad_reg_dev,
+                             const float *upstream_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

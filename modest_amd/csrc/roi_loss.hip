@@ -1,0 +1,361 @@
+// Loss of OpenPCDet's RoI heads with its gradients (RoIHeadTemplate.get_loss, pcdet/models/roi_heads/roi_head_template.py:133-228,
+// over ResidualCoder of pcdet/utils/box_coder_utils.py, WeightedSmoothL1Loss and get_corner_loss_lidar of
+// pcdet/utils/loss_utils.py), hand-written for gfx950.  Two entry points (include/modest_hip.h, "a35"): enqueue only, no
+// synchronise, no context, no device allocation, nothing read back.
+//
+// The encoded targets, the foreground subset, the rotation matrices and the three (fg, 8, 3) corner tensors of the reference
+// are never formed; a row that is not foreground reads nothing for the box terms and costs them its zero gradient row.  Kernels:
+//   rl_loss    one lane per RoI, 256 per workgroup.  Every workgroup first counts the foreground rows (reg_valid_mask > 0) and
+//              the valid class rows (label >= 0) of the WHOLE arrays with ballot + popcount into LDS integers (the arrays are R
+//              words and live in L2; no count kernel, no atomic), then the lane computes its row's three terms and writes its
+//              gradient rows; the three sums of the workgroup go through the fixed tree of section 7p (xor butterfly over the
+//              wavefront, (w0 + w1) + (w2 + w3) in LDS) into the partials array;
+//   rl_finish  one workgroup: lane t adds partials t, t + 256, ... in ascending order, then the same tree, then the table;
+//   rl_scale   (modest_roi_loss_backward) the two gradient buffers times the upstream gradient read from the device.
+// No float atomics: no result depends on arrival order.  The arithmetic is the contract of DESIGN.md section 7q: float32, one
+// rounding per operation in the written order (built with -ffp-contract=off), exp / log / log1p / sin / cos and the sigmoid as
+// the double function rounded once, sqrt and / correctly rounded; the gradient follows autograd's own chain through the
+// reference's expression, path by path.  The 8 corners and code columns 0 .. 6 are unrolled: no indexed per-thread array.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "common.h"
+#include "modest_hip.h"
+#include "trig_f32.h"
+
+namespace {
+
+constexpr int RL_T = 256;          // lanes (rows) per workgroup
+constexpr int RL_WAVES = RL_T / 64;
+constexpr int RL_MAX_CODE = 16;
+constexpr int64_t RL_MAX_ROWS = 1 << 20;   // every workgroup counts over all rows: R^2 / 256 reads
+
+__device__ __forceinline__ float exp_f32(float x) { return (float)exp((double)x); }
+__device__ __forceinline__ float log_f32(float x) { return (float)log((double)x); }
+__device__ __forceinline__ float log1p_f32(float x) { return (float)log1p((double)x); }
+__device__ __forceinline__ float sigmoid_f32(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
+// torch's sgn of a real: (0 < x) - (x < 0), so 0 for a NaN
+__device__ __forceinline__ float sign_f32(float x) { return (float)((0.f < x) - (x < 0.f)); }
+// torch's clamp(min=lo): a NaN stays a NaN
+__device__ __forceinline__ float at_least(float v, float lo) { return v < lo ? lo : v; }
+
+struct RoiLossParams {
+    int64_t r, blocks;
+    int code, label_kind, mask64, corner, l1, want_grad;   // label_kind 0 int32, 1 int64, 2 float32
+    int64_t gt_stride, src_stride;
+    const float *cls, *reg, *gt, *src, *rois, *cw;
+    const void *labels, *mask;
+    float beta, half_beta, w_cls, w_reg, w_corner, tiny, pi, floor100, eps12;
+    float *gcls, *greg, *out;
+    float *part;                   // (3, blocks) workgroup sums
+};
+
+__device__ __forceinline__ bool fg_at(const RoiLossParams &p, int64_t row) {
+    return p.mask64 ? static_cast<const int64_t *>(p.mask)[row] > 0 : static_cast<const int32_t *>(p.mask)[row] > 0;
+}
+
+// -> the label as float32 (what .float() gives); valid: label >= 0
+__device__ __forceinline__ float label_at(const RoiLossParams &p, int64_t row, bool &valid) {
+    if (p.label_kind == 1) {
+        const int64_t v = static_cast<const int64_t *>(p.labels)[row];
+        valid = v >= 0;
+        return (float)v;
+    }
+    if (p.label_kind == 2) {
+        const float v = static_cast<const float *>(p.labels)[row];
+        valid = v >= 0.f;
+        return v;
+    }
+    const int32_t v = static_cast<const int32_t *>(p.labels)[row];
+    valid = v >= 0;
+    return (float)v;
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+
+// column k of ResidualCoder.encode_torch of the canonical gt against the roi with centre and heading zeroed
+__device__ __forceinline__ float encode_col(const RoiLossParams &p, int k, const float *g, const float *roi, float diag_c, float dz_c) {
+    if (k < 2) return g[k] / diag_c;
+    if (k == 2) return g[2] / dz_c;
+    if (k < 6) return log_f32(at_least(g[k], p.tiny) / at_least(roi[k], p.tiny));
+    if (k == 6) return g[6];
+    return g[k] - roi[k];
+}
+
+// the smooth-L1 term of one column: -> its value, its gradient to the input through *grad
+__device__ __forceinline__ float sl1_col(const RoiLossParams &p, int k, float in, float tg, float gl, float *grad) {
+    const bool replaced = tg != tg;           // a NaN target is replaced by the input
+    if (replaced) tg = in;
+    const float cw = p.cw[k];
+    const float d = (in - tg) * cw;
+    const float nrm = fabsf(d);
+    const bool quad = !p.l1 && nrm < p.beta;
+    const float v = p.l1 ? nrm : (quad ? ((0.5f * (nrm * nrm)) / p.beta) : (nrm - p.half_beta));
+    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : gl;
+    const float g_d = (g_n * sign_f32(d)) * cw;
+    *grad = replaced ? g_d + (-g_d) : g_d;    // where(isnan): the target's share goes to the input and cancels
+    return v;
+}
+
+__global__ __launch_bounds__(RL_T) void rl_loss(RoiLossParams p) {
+    __shared__ int s_cnt[2][RL_WAVES];
+    __shared__ float s_sum[3][RL_WAVES];
+    const int tid = threadIdx.x;
+    // ---- the two counts over the whole arrays
+    int n_fg = 0, n_valid = 0;
+    for (int64_t j0 = 0; j0 < p.r; j0 += RL_T) {
+        const int64_t j = j0 + tid;
+        bool valid = false, fg = false;
+        if (j < p.r) {
+            label_at(p, j, valid);
+            fg = fg_at(p, j);
+        }
+        n_fg += __popcll(__ballot(fg));
+        n_valid += __popcll(__ballot(valid));
+    }
+    if ((tid & 63) == 0) {
+        s_cnt[0][tid >> 6] = n_fg;
+        s_cnt[1][tid >> 6] = n_valid;
+    }
+    __syncthreads();
+    const int fg_sum = (s_cnt[0][0] + s_cnt[0][1]) + (s_cnt[0][2] + s_cnt[0][3]);
+    const int valid_sum = (s_cnt[1][0] + s_cnt[1][1]) + (s_cnt[1][2] + s_cnt[1][3]);
+
+    const int64_t row = (int64_t)blockIdx.x * RL_T + tid;
+    float sum_cls = 0.f, sum_reg = 0.f, sum_corner = 0.f;
+    if (row < p.r) {
+        // ---- classification: binary cross entropy of the sigmoid
+        bool valid;
+        const float t = label_at(p, row, valid);
+        if (valid) {
+            const float x = p.cls[row];
+            const float s = sigmoid_f32(x);
+            const float la = at_least(log1p_f32(-s), p.floor100), lb = at_least(log_f32(s), p.floor100);
+            sum_cls = (t - 1.f) * la - t * lb;
+            if (p.want_grad) {
+                const float g0 = p.w_cls / fmaxf((float)valid_sum, 1.f);
+                const float oms = 1.f - s;
+                const float g_s = (g0 * (s - t)) / at_least(oms * s, p.eps12);
+                p.gcls[row] = (g_s * oms) * s;
+            }
+        } else if (p.want_grad) {
+            p.gcls[row] = 0.f;
+        }
+        // ---- the box terms, foreground rows only
+        float *gr = p.want_grad ? p.greg + row * p.code : nullptr;
+        if (fg_at(p, row)) {
+            const float *in = p.reg + row * p.code, *roi = p.rois + row * p.code;
+            const float *g = p.gt + row * p.gt_stride;
+            const float rdx = roi[3], rdy = roi[4], rdz = roi[5];
+            float gc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // the corner term's share, constant indices only
+            if (p.corner) {
+                const float *q = p.src + row * p.src_stride;
+                const float rh = roi[6];
+                const float diag = sqrtf(rdx * rdx + rdy * rdy);      // the decode does not clamp the roi's sizes
+                const float e3 = exp_f32(in[3]), e4 = exp_f32(in[4]), e5 = exp_f32(in[5]);
+                const float x0 = in[0] * diag, y0 = in[1] * diag, z0 = in[2] * rdz;
+                const float dx = e3 * rdx, dy = e4 * rdy, dz = e5 * rdz;
+                const float hp = in[6] + rh;
+                const float cr = modest::cos_f32(rh), sr = modest::sin_f32(rh);
+                const float cx = (x0 * cr - y0 * sr) + roi[0], cy = (x0 * sr + y0 * cr) + roi[1], cz = z0 + roi[2];
+                const float cp = modest::cos_f32(hp), sp = modest::sin_f32(hp);
+                const float qx = q[0], qy = q[1], qz = q[2], qdx = q[3], qdy = q[4], qdz = q[5], qh = q[6];
+                const float cg = modest::cos_f32(qh), sg = modest::sin_f32(qh);
+                const float qf = qh + p.pi;
+                const float cf = modest::cos_f32(qf), sf = modest::sin_f32(qf);
+                const float g_row = p.w_corner / (float)fg_sum;
+                const float g_c = g_row / 8.f;
+                float csum = 0.f, gcx = 0.f, gcy = 0.f, gcz = 0.f, gdx = 0.f, gdy = 0.f, gdz = 0.f;
+                float G00 = 0.f, G01 = 0.f, G10 = 0.f, G11 = 0.f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float ax = (k & 3) < 2 ? 0.5f : -0.5f;
+                    const float ay = ((k & 3) == 0 || (k & 3) == 3) ? 0.5f : -0.5f;
+                    const float az = k < 4 ? -0.5f : 0.5f;
+                    const float lx = dx * ax, ly = dy * ay, lz = dz * az;
+                    const float PX = (lx * cp - ly * sp) + cx, PY = (lx * sp + ly * cp) + cy, PZ = lz + cz;
+                    const float mx = qdx * ax, my = qdy * ay, mz = qdz * az;
+                    const float GX = (mx * cg - my * sg) + qx, GY = (mx * sg + my * cg) + qy, GZ = mz + qz;
+                    const float FX = (mx * cf - my * sf) + qx, FY = (mx * sf + my * cf) + qy;
+                    const float ax_ = PX - GX, ay_ = PY - GY, az_ = PZ - GZ;
+                    const float bx_ = PX - FX, by_ = PY - FY;
+                    const float na = sqrtf((ax_ * ax_ + ay_ * ay_) + az_ * az_);
+                    const float nb = sqrtf((bx_ * bx_ + by_ * by_) + az_ * az_);
+                    const float m = nb < na ? nb : na;
+                    const bool quad = m < 1.f;
+                    csum = csum + (quad ? 0.5f * (m * m) : m - 0.5f);
+                    if (gr) {
+                        const float g_m = (quad ? (g_c * 0.5f) * (2.f * m) : g_c) * sign_f32(m);
+                        const float g_h = na == nb ? g_m / 2.f : g_m;          // min of two equal values: half to each side
+                        const float ga = na > nb ? 0.f : g_h, gb = na < nb ? 0.f : g_h;
+                        // the norm of a zero vector hands on 0
+                        const float uax = na == 0.f ? 0.f : ax_ / na, uay = na == 0.f ? 0.f : ay_ / na, uaz = na == 0.f ? 0.f : az_ / na;
+                        const float ubx = nb == 0.f ? 0.f : bx_ / nb, uby = nb == 0.f ? 0.f : by_ / nb, ubz = nb == 0.f ? 0.f : az_ / nb;
+                        const float gPX = ga * uax + gb * ubx, gPY = ga * uay + gb * uby, gPZ = ga * uaz + gb * ubz;
+                        gcx = gcx + gPX; gcy = gcy + gPY; gcz = gcz + gPZ;
+                        G00 = G00 + lx * gPX; G11 = G11 + ly * gPY; G01 = G01 + lx * gPY; G10 = G10 + ly * gPX;
+                        const float glx = gPX * cp + gPY * sp, gly = gPY * cp - gPX * sp;
+                        gdx = gdx + glx * ax; gdy = gdy + gly * ay; gdz = gdz + gPZ * az;
+                    }
+                }
+                sum_corner = csum / 8.f;
+                if (gr) {
+                    const float g_cos = G00 + G11, g_sin = G01 - G10;
+                    const float gx0 = gcx * cr + gcy * sr, gy0 = gcy * cr - gcx * sr;
+                    gc[0] = gx0 * diag;
+                    gc[1] = gy0 * diag;
+                    gc[2] = gcz * rdz;
+                    gc[3] = (gdx * rdx) * e3;
+                    gc[4] = (gdy * rdy) * e4;
+                    gc[5] = (gdz * rdz) * e5;
+                    gc[6] = g_sin * cp - g_cos * sp;
+                }
+            }
+            // ---- smooth L1 of the encoding, columns in order
+            const float ca = at_least(rdx, p.tiny), cb = at_least(rdy, p.tiny), dz_c = at_least(rdz, p.tiny);
+            const float diag_c = sqrtf(ca * ca + cb * cb);
+            const float gl = p.w_reg / fmaxf((float)fg_sum, 1.f);
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                float gk;
+                sum_reg = sum_reg + sl1_col(p, k, in[k], encode_col(p, k, g, roi, diag_c, dz_c), gl, &gk);
+                if (gr) gr[k] = gk + gc[k];
+            }
+            for (int k = 7; k < p.code; ++k) {
+                float gk;
+                sum_reg = sum_reg + sl1_col(p, k, in[k], encode_col(p, k, g, roi, diag_c, dz_c), gl, &gk);
+                if (gr) gr[k] = gk;
+            }
+        } else if (gr) {
+            for (int k = 0; k < p.code; ++k) gr[k] = 0.f;
+        }
+    }
+    const float a = wave_sum(sum_cls), l = wave_sum(sum_reg), c = wave_sum(sum_corner);
+    if ((tid & 63) == 0) {
+        s_sum[0][tid >> 6] = a;
+        s_sum[1][tid >> 6] = l;
+        s_sum[2][tid >> 6] = c;
+    }
+    __syncthreads();
+    if (tid < 3) p.part[tid * p.blocks + blockIdx.x] = (s_sum[tid][0] + s_sum[tid][1]) + (s_sum[tid][2] + s_sum[tid][3]);
+    if (blockIdx.x == 0 && tid == 0) {
+        p.out[4] = (float)fg_sum;
+        p.out[5] = (float)valid_sum;
+    }
+}
+
+__global__ __launch_bounds__(RL_T) void rl_finish(RoiLossParams p) {
+    __shared__ float s_sum[3][RL_WAVES];
+    const int tid = threadIdx.x;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    // partials t, t + 256, ... in ascending order; an accumulator that starts at +0 is never -0
+    for (int64_t j = tid; j < p.blocks; j += RL_T) {
+        a0 = a0 + p.part[j];
+        a1 = a1 + p.part[p.blocks + j];
+        a2 = a2 + p.part[2 * p.blocks + j];
+    }
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
+    if ((tid & 63) == 0) {
+        s_sum[0][tid >> 6] = a0;
+        s_sum[1][tid >> 6] = a1;
+        s_sum[2][tid >> 6] = a2;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float v0 = (s_sum[0][0] + s_sum[0][1]) + (s_sum[0][2] + s_sum[0][3]);
+        const float v1 = (s_sum[1][0] + s_sum[1][1]) + (s_sum[1][2] + s_sum[1][3]);
+        const float v2 = (s_sum[2][0] + s_sum[2][1]) + (s_sum[2][2] + s_sum[2][3]);
+        const float fg = p.blocks > 0 ? p.out[4] : 0.f, valid = p.blocks > 0 ? p.out[5] : 0.f;   // written by rl_loss, earlier on the stream
+        const float cls = (v0 / fmaxf(valid, 1.f)) * p.w_cls;
+        const float reg = (v1 / fmaxf(fg, 1.f)) * p.w_reg;
+        const bool with_corner = p.corner && fg > 0.f;
+        const float corner = with_corner ? (v2 / fg) * p.w_corner : 0.f;
+        p.out[0] = cls;
+        p.out[1] = reg;
+        p.out[2] = corner;
+        p.out[3] = with_corner ? cls + (reg + corner) : cls + reg;
+        p.out[4] = fg;
+        p.out[5] = valid;
+    }
+}
+
+__global__ __launch_bounds__(RL_T) void rl_scale(int64_t n0, int64_t n1, float *__restrict__ g0, float *__restrict__ g1,
+                                                const float *__restrict__ upstream) {
+    const float u = upstream[0];
+    const int64_t i = (int64_t)blockIdx.x * RL_T + threadIdx.x;
+    if (i < n0) g0[i] = g0[i] * u;
+    else if (i < n0 + n1) g1[i - n0] = g1[i - n0] * u;
+}
+
+int64_t blocks_of(int64_t n) { return (n + RL_T - 1) / RL_T; }
+size_t ws_total(int64_t r) { return arena_sz(4 * 3 * (size_t)(blocks_of(r) > 0 ? blocks_of(r) : 1)); }
+
+}  // namespace
+
+extern "C" int64_t modest_roi_loss_max_rows(void) { return RL_MAX_ROWS; }
+
+extern "C" int64_t modest_roi_loss_workspace_bytes(int64_t n_rows) {
+    if (n_rows < 0 || n_rows > RL_MAX_ROWS) {
+        modest_set_error("modest_roi_loss_workspace_bytes: requirement failed: 0 <= n_rows <= 2^20");
+        return MODEST_ERR_ARG;
+    }
+    return (int64_t)ws_total(n_rows);
+}
+
+extern "C" int modest_roi_loss(int64_t n_rows, int code, const float *rcnn_cls_dev, const float *rcnn_reg_dev,
+                               const void *cls_labels_dev, int label_kind, const void *reg_valid_mask_dev, int mask_int64,
+                               const float *gt_of_rois_dev, int64_t gt_row_stride, const float *gt_of_rois_src_dev,
+                               int64_t src_row_stride, const float *rois_dev, const float *code_weights_dev, float beta,
+                               float cls_weight, float reg_weight, float corner_weight, int corner, float *table_dev,
+                               float *grad_cls_dev, float *grad_reg_dev, void *workspace_dev, int64_t workspace_bytes,
+                               void *stream) {
+    MODEST_REQUIRE(n_rows >= 0 && n_rows <= RL_MAX_ROWS, "n_rows between 0 and 2^20 (every workgroup counts over all rows)");
+    MODEST_REQUIRE(code >= 7 && code <= RL_MAX_CODE, "code size between 7 and 16");
+    MODEST_REQUIRE(label_kind >= 0 && label_kind <= 2, "label_kind 0 (int32), 1 (int64) or 2 (float32)");
+    MODEST_REQUIRE(gt_row_stride >= code && src_row_stride >= code, "a row stride of gt_of_rois / gt_of_rois_src below the code size");
+    MODEST_REQUIRE(table_dev && workspace_dev && ((uintptr_t)workspace_dev & 3) == 0, "NULL or unaligned buffer");
+    MODEST_REQUIRE(workspace_bytes >= (int64_t)ws_total(n_rows), "workspace smaller than modest_roi_loss_workspace_bytes");
+    const bool want = grad_cls_dev != nullptr;
+    MODEST_REQUIRE(want == (grad_reg_dev != nullptr), "the gradient buffers come together");
+    MODEST_REQUIRE(n_rows == 0 || (rcnn_cls_dev && rcnn_reg_dev && cls_labels_dev && reg_valid_mask_dev && gt_of_rois_dev &&
+                                   gt_of_rois_src_dev && rois_dev && code_weights_dev), "NULL buffer");
+    RoiLossParams p;
+    p.r = n_rows; p.blocks = blocks_of(n_rows);
+    p.code = code; p.label_kind = label_kind; p.mask64 = mask_int64 ? 1 : 0; p.corner = corner ? 1 : 0;
+    p.l1 = (double)beta < 1e-5 ? 1 : 0;
+    p.want_grad = want ? 1 : 0;
+    p.gt_stride = gt_row_stride; p.src_stride = src_row_stride;
+    p.cls = rcnn_cls_dev; p.reg = rcnn_reg_dev; p.gt = gt_of_rois_dev; p.src = gt_of_rois_src_dev; p.rois = rois_dev;
+    p.cw = code_weights_dev; p.labels = cls_labels_dev; p.mask = reg_valid_mask_dev;
+    p.beta = beta; p.half_beta = (float)(0.5 * (double)beta);
+    p.w_cls = cls_weight; p.w_reg = reg_weight; p.w_corner = corner_weight;
+    p.tiny = (float)1e-5; p.pi = (float)3.14159265358979323846; p.floor100 = -100.f; p.eps12 = (float)1e-12;
+    p.gcls = grad_cls_dev; p.greg = grad_reg_dev; p.out = table_dev;
+    p.part = static_cast<float *>(workspace_dev);
+    hipStream_t s = as_stream(stream);
+    if (p.blocks > 0) {
+        rl_loss<<<(unsigned)p.blocks, RL_T, 0, s>>>(p);
+        MODEST_HIP_CHECK(hipGetLastError());
+    }
+    rl_finish<<<1, RL_T, 0, s>>>(p);
+    MODEST_HIP_CHECK(hipGetLastError());
+    return MODEST_OK;
+}
+
+extern "C" int modest_roi_loss_backward(int64_t n_cls, int64_t n_reg, float *grad_cls_dev, float *grad_reg_dev,
+                                        const float *upstream_dev, void *stream) {
+    MODEST_REQUIRE(n_cls >= 0 && n_reg >= 0, "negative size");
+    MODEST_REQUIRE(n_cls <= RL_MAX_ROWS && n_reg <= RL_MAX_ROWS * RL_MAX_CODE, "more gradient elements than 2^20 rows of 16 columns");
+    MODEST_REQUIRE((n_cls == 0 || grad_cls_dev) && (n_reg == 0 || grad_reg_dev), "NULL buffer");
+    const int64_t total = n_cls + n_reg;
+    if (total == 0) return MODEST_OK;
+    MODEST_REQUIRE(upstream_dev, "NULL upstream gradient");
+    rl_scale<<<(unsigned)blocks_of(total), RL_T, 0, as_stream(stream)>>>(n_cls, n_reg, grad_cls_dev, grad_reg_dev, upstream_dev);
+    MODEST_HIP_CHECK(hipGetLastError());
+    return MODEST_OK;
+}

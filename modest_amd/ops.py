@@ -2150,3 +2150,119 @@ def anchor_loss_backward(grads, upstream: torch.Tensor):
         check(load().modest_anchor_loss_backward(num(gcls), num(gbox), num(gdir), ptr(gcls), ptr(gbox), ptr(gdir),
                                                  upstream.data_ptr(), _stream()), "modest_anchor_loss_backward")
     return grads
+
+
+# --------------------------------------------------------------------------- RoI-head loss
+ROI_LOSS_MAX_ROWS = 1 << 20     # R = B x ROI_PER_IMAGE: every workgroup counts over all rows
+ROI_LOSS_MIN_CODE = 7           # box code columns
+ROI_LOSS_MAX_CODE = 16
+ROI_LOSS_TABLE = ("rcnn_loss_cls", "rcnn_loss_reg", "rcnn_loss_corner", "rcnn_loss", "fg_sum", "cls_valid")
+_ROI_LOSS_LABELS = {torch.int32: 0, torch.int64: 1, torch.float32: 2}
+
+
+def roi_loss_workspace_bytes(n_rows: int) -> int:
+    nb = int(load().modest_roi_loss_workspace_bytes(int(n_rows)))
+    if nb < 0:
+        check(nb, "modest_roi_loss_workspace_bytes")
+    return nb
+
+
+def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: torch.Tensor, reg_valid_mask: torch.Tensor,
+             gt_of_rois: torch.Tensor, gt_of_rois_src: torch.Tensor, rois: torch.Tensor, code_weights: torch.Tensor, *,
+             beta: float = 1.0 / 9.0, cls_weight: float = 1.0, reg_weight: float = 1.0, corner_weight: float = 1.0,
+             corner: bool = True, want_grad: bool = True, workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_roi_loss on PyTorch's current stream: enqueue only, nothing is read back.
+    rcnn_cls (R) or (R, 1) logits and rcnn_reg (R, code): float32 device tensors, made contiguous when they are not;
+    rcnn_cls_labels (R) int32, int64 or float32 (a row counts iff label >= 0); reg_valid_mask (R) int32 or int64 (foreground
+    iff > 0); gt_of_rois and gt_of_rois_src (R, >= code) float32 with unit column stride, read through their row strides;
+    rois (R, code) and code_weights (code) float32, contiguous.  The scalars are rounded to float32, as torch rounds a Python
+    scalar that meets a float32 tensor.
+    -> (table (6) float32 [rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner, rcnn_loss, fg_sum, cls_valid], grads): grads is None
+    without want_grad, else (grad_cls (R), grad_reg (R, code)), d rcnn_loss / d prediction, every element written.
+    `out` = (table, grad_cls, grad_reg) supplies the buffers (the gradients None without want_grad)."""
+    named = (("rcnn_cls", rcnn_cls), ("rcnn_reg", rcnn_reg), ("rcnn_cls_labels", rcnn_cls_labels), ("reg_valid_mask", reg_valid_mask),
+             ("gt_of_rois", gt_of_rois), ("gt_of_rois_src", gt_of_rois_src), ("rois", rois), ("code_weights", code_weights))
+    for name, t in named:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if name == "rcnn_cls_labels":
+            if t.dtype not in _ROI_LOSS_LABELS:
+                raise TypeError(f"rcnn_cls_labels must be int32, int64 or float32, got {t.dtype}")
+        elif name == "reg_valid_mask":
+            if t.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"reg_valid_mask must be int32 or int64, got {t.dtype}")
+        elif t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    dev = rcnn_cls.device
+    if rcnn_reg.ndim != 2:
+        raise ValueError(f"rcnn_reg {tuple(rcnn_reg.shape)} must be (R, code)")
+    R, code = (int(v) for v in rcnn_reg.shape)
+    if code < ROI_LOSS_MIN_CODE or code > ROI_LOSS_MAX_CODE:
+        raise ValueError(f"code size = {code} is outside the limit of {ROI_LOSS_MIN_CODE} .. {ROI_LOSS_MAX_CODE} box columns")
+    if R > ROI_LOSS_MAX_ROWS:
+        raise ValueError(f"rcnn_reg has {R} rows, above the limit of {ROI_LOSS_MAX_ROWS} rows per call")
+    if rcnn_cls.numel() != R:
+        raise ValueError(f"rcnn_cls has {rcnn_cls.numel()} elements, rcnn_reg {R} rows")
+    for name, t in (("rcnn_cls_labels", rcnn_cls_labels), ("reg_valid_mask", reg_valid_mask)):
+        if tuple(t.shape) != (R,) or not t.is_contiguous():
+            raise ValueError(f"{name} {tuple(t.shape)} must be a contiguous ({R},)")
+    for name, t in (("gt_of_rois", gt_of_rois), ("gt_of_rois_src", gt_of_rois_src)):
+        if t.ndim != 2 or t.shape[0] != R or t.shape[1] < code:
+            raise ValueError(f"{name} {tuple(t.shape)} must be (R, >= code) = ({R}, >= {code})")
+        if R and (t.stride(1) != 1 or (R > 1 and t.stride(0) < code)):
+            raise ValueError(f"{name} must have unit column stride and a row stride of at least {code}, got strides {tuple(t.stride())}")
+    if tuple(rois.shape) != (R, code) or not rois.is_contiguous():
+        raise ValueError(f"rois {tuple(rois.shape)} must be a contiguous (R, code) = ({R}, {code})")
+    if tuple(code_weights.shape) != (code,) or not code_weights.is_contiguous():
+        raise ValueError(f"code_weights {tuple(code_weights.shape)} must be a contiguous (code,) = ({code},)")
+    for name, t in named[1:]:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, rcnn_cls on {dev}")
+    cls, reg = rcnn_cls.reshape(-1).contiguous(), rcnn_reg.contiguous()
+    want = (("table", (6,)), ("grad_cls", (R,)), ("grad_reg", (R, code)))
+    if out is None:
+        out = [torch.empty(shape, dtype=torch.float32, device=dev) if (i == 0 or want_grad) else None
+               for i, (_, shape) in enumerate(want)]
+    if len(out) != 3:
+        raise ValueError("out must be (table, grad_cls, grad_reg)")
+    for i, (t, (name, shape)) in enumerate(zip(out, want)):
+        need = i == 0 or want_grad
+        if (t is not None) != need:
+            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
+        if t is not None:
+            _dev(t, torch.float32, f"out {name}")
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
+    table, gcls, greg = out
+    nbytes = roi_loss_workspace_bytes(R)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    stride = lambda t: int(t.stride(0)) if R > 1 else int(t.shape[1])      # noqa: E731
+    with torch.cuda.device(dev):
+        check(load().modest_roi_loss(R, code, ptr(cls), ptr(reg), ptr(rcnn_cls_labels), _ROI_LOSS_LABELS[rcnn_cls_labels.dtype],
+                                     ptr(reg_valid_mask), int(reg_valid_mask.dtype == torch.int64), ptr(gt_of_rois),
+                                     stride(gt_of_rois), ptr(gt_of_rois_src), stride(gt_of_rois_src), ptr(rois),
+                                     ptr(code_weights), float(beta), float(cls_weight), float(reg_weight), float(corner_weight),
+                                     int(bool(corner)), ptr(table), ptr(gcls), ptr(greg), workspace.data_ptr(),
+                                     workspace.numel(), _stream()), "modest_roi_loss")
+    return table, ((gcls, greg) if want_grad else None)
+
+
+def roi_loss_backward(grads, upstream: torch.Tensor):
+    """modest_roi_loss_backward on PyTorch's current stream: the two gradient buffers of `roi_loss` times the float32 device
+    scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
+    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("upstream must be a float32 device tensor of one element")
+    if len(grads) != 2:
+        raise ValueError("grads must be (grad_cls, grad_reg)")
+    for g in grads:
+        _dev(g, torch.float32, "a gradient buffer")
+        if g.device != upstream.device:
+            raise ValueError("the gradient buffers and upstream are on different devices")
+    gcls, greg = grads
+    with torch.cuda.device(upstream.device):
+        check(load().modest_roi_loss_backward(int(gcls.numel()), int(greg.numel()), gcls.data_ptr(), greg.data_ptr(),
+                                              upstream.data_ptr(), _stream()), "modest_roi_loss_backward")
+    return grads

@@ -53,6 +53,12 @@ test-time post-processing of every detector in one call -
 the anchor heads with its gradients in one call -- on ``AnchorHeadTemplate`` of
 ``pcdet.models.dense_heads.anchor_head_template``, imported for it if it is not yet; a head that overrides a part of the
 loss (``AnchorHeadMulti``) reaches the method that was replaced.
+
+``bind_roi_loss()``, a function of its own like the others, sets ``modest_amd.utils.roi_head_loss.get_loss`` -- the loss of
+the RoI heads with its gradients in one call -- on ``RoIHeadTemplate`` of
+``pcdet.models.roi_heads.roi_head_template``, imported for it if it is not yet; a head that overrides
+``get_box_reg_layer_loss`` or ``get_box_cls_layer_loss`` reaches the method that was replaced, and a head class with a
+``get_loss`` of its own (``SECONDHead``) keeps it.
 """
 import importlib
 import importlib.util
@@ -88,6 +94,8 @@ POST_PROCESSING_NAME = "pcdet.models.detectors.detector3d_template"
 POST_PROCESSING = "modest_amd.utils.post_processing"   # its method set on Detector3DTemplate by bind_post_processing()
 ANCHOR_LOSS_NAME = "pcdet.models.dense_heads.anchor_head_template"
 ANCHOR_LOSS = "modest_amd.utils.anchor_head_loss"      # its method set on AnchorHeadTemplate by bind_anchor_loss()
+ROI_LOSS_NAME = PROPOSAL_LAYER_NAME
+ROI_LOSS = "modest_amd.utils.roi_head_loss"            # its method set on RoIHeadTemplate by bind_roi_loss()
 
 
 class StandIn(types.ModuleType):
@@ -248,6 +256,26 @@ def bind_anchor_loss():
     if head is None:
         return None
     importlib.import_module(ANCHOR_LOSS).bind(head)
+    return mod
+
+
+def bind_roi_loss():
+    """RoIHeadTemplate.get_loss := modest_amd.utils.roi_head_loss.get_loss -- the loss of the RoI heads with its gradients
+     -- in the reference's module if it is imported or can be -> that module, or None.  A function of
+    its own: install() and what it returns stay as they are.  Only the template's own method is set, and the one it had is
+    kept: a head that overrides get_box_reg_layer_loss or get_box_cls_layer_loss is handed to it, and a head class with a
+    get_loss of its own (SECONDHead) keeps that.  Idempotent; before or after ``import pcdet.models``; touches no GPU
+    state."""
+    mod = sys.modules.get(ROI_LOSS_NAME)
+    if mod is None:
+        try:
+            mod = importlib.import_module(ROI_LOSS_NAME)
+        except ImportError:
+            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
+    head = getattr(mod, "RoIHeadTemplate", None)
+    if head is None:
+        return None
+    importlib.import_module(ROI_LOSS).bind(head)
     return mod
 
 
