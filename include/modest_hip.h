@@ -1386,6 +1386,49 @@ int modest_roi_loss(int64_t n_rows, int code, const float *rcnn_cls_dev, const f
 int modest_roi_loss_backward(int64_t n_cls, int64_t n_reg, float *grad_cls_dev, float *grad_reg_dev,
                              const float *upstream_dev, void *stream);
 
+/* ---- a36 point-head loss with its gradients (PointHeadBox / PointIntraPartOffsetHead / PointHeadSimple .get_loss over
+ * get_cls_layer_loss, get_part_layer_loss and get_box_layer_loss of PointHeadTemplate) ------------------------
+ * The losses of all N points of a stacked batch and, where wanted, their gradients in one call: enqueue only -- no
+ * synchronise, no context, no device allocation, nothing read back.  Contiguous device memory, float32 unless said:
+ *   cls_preds (N, num_class) logits,
+ *   labels (N) int32, or int64 with labels_int64 != 0: < 0 ignored, 0 background, c + 1 class c (strictly: no override for
+ *   num_class == 1; a label above num_class matches no class and counts as a positive),
+ *   part_preds (N, 3) logits and part_labels (N, 3), both or both NULL (no part term),
+ *   box_preds (N, code), box_labels (N, code) and code_weights (code), all three or all NULL (no box term).
+ * P = the number of labels > 0 over ALL N points (not per sample; nothing is divided by a batch size), w = 1.0f / max(P, 1):
+ *   classification  weight w where label >= 0, else 0; t = 1 iff label == c + 1, s = sigmoid(x), aw = 0.25 t + 0.75 (1 - t),
+ *                   pt = t (1 - s) + (1 - t) s, bce = max(x, 0) - x t + log1p(exp(-|x|)), value ((aw pt pt) bce) w, a point's
+ *                   columns added in class order; point_loss_cls = sum cls_weight;
+ *   part            positive rows only; per column s = sigmoid(x), (t - 1) max(log1p(-s), -100) - t max(log(s), -100), the
+ *                   three columns added in order; point_loss_part = (sum / float(3 max(P, 1))) part_weight;
+ *   box             positive rows only; a NaN target is replaced by the input; d = (in - tg) code_weight, n = |d|, value
+ *                   (n < beta ? 0.5 n n / beta : n - 0.5 beta) w, plain n w with beta < 1e-5, the columns added in order;
+ *                   point_loss_box = sum box_weight;
+ *   point_loss      cls, (cls + part), (cls + box) or ((cls + part) + box): absent terms are skipped.
+ * float32 in this order, one rounding per operation, Python's scalars rounded to float32 first; exp, log, log1p and the
+ * sigmoid are the double function rounded once; / is correctly rounded.  The sums run over the fixed tree of 7p: no float
+ * atomics, the same bits at every run.  A row that is not positive is not read for the part and box terms.
+ * table (5): point_loss_cls, point_loss_part, point_loss_box (0 for an absent term), point_loss, point_pos_num = P.
+ * grad_cls / grad_part / grad_box: grad_cls NULL (no gradients, the others NULL too), or one buffer of the prediction's shape
+ * per term present (NULL for an absent term) that receives d point_loss / d prediction as autograd's chain through the
+ * expressions above gives it (at a logit of +-0 the bce derivative is 1 - t; the part gradient is (g (s - t)) / max((1 - s) s,
+ * 1e-12) through the sigmoid with g = part_weight / float(3 max(P, 1))); EVERY element is written, the part and box rows of
+ * points that are not positive with zeros.
+ * Limits (the call fails and launches nothing): n_rows <= modest_point_loss_max_rows() = 2^24 (P stays exact in float32),
+ * 1 <= num_class <= 32, 1 <= code <= 16.  workspace 4-byte aligned, modest_point_loss_workspace_bytes(n_rows) bytes, need
+ * not be initialised.
+ * modest_point_loss_backward multiplies the three gradient buffers (n_cls, n_part, n_box elements; 0 for an absent term) in
+ * place by the float32 upstream gradient at upstream_dev, one rounding per element: enqueue only.                             */
+int64_t modest_point_loss_max_rows(void);
+int64_t modest_point_loss_workspace_bytes(int64_t n_rows);
+int modest_point_loss(int64_t n_rows, int num_class, int code, const float *cls_preds_dev, const void *labels_dev,
+                      int labels_int64, const float *part_preds_dev, const float *part_labels_dev,
+                      const float *box_preds_dev, const float *box_labels_dev, const float *code_weights_dev, float beta,
+                      float cls_weight, float part_weight, float box_weight, float *grad_cls_dev, float *grad_part_dev,
+                      float *grad_box_dev, float *table_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_point_loss_backward(int64_t n_cls, int64_t n_part, int64_t n_box, float *grad_cls_dev, float *grad_part_dev,
+                               float *grad_box_dev, const float *upstream_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,11 @@ SIGNATURES = {
     "modest_roi_loss": (C.c_int, [C.c_int64, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, VP, C.c_int64, VP, C.c_int64, VP, VP,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, VP, VP, VP, VP, C.c_int64, VP]),
     "modest_roi_loss_backward": (C.c_int, [C.c_int64, C.c_int64, VP, VP, VP, VP]),
+    "modest_point_loss_max_rows": (C.c_int64, []),
+    "modest_point_loss_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "modest_point_loss": (C.c_int, [C.c_int64, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, VP, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_point_loss_backward": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

@@ -2266,3 +2266,131 @@ def roi_loss_backward(grads, upstream: torch.Tensor):
         check(load().modest_roi_loss_backward(int(gcls.numel()), int(greg.numel()), gcls.data_ptr(), greg.data_ptr(),
                                               upstream.data_ptr(), _stream()), "modest_roi_loss_backward")
     return grads
+
+
+# --------------------------------------------------------------------------- point-head loss
+POINT_LOSS_MAX_ROWS = 1 << 24   # N of the stacked batch: the count of positives stays exact in float32
+POINT_LOSS_MAX_CLASS = 32       # class columns of a point
+POINT_LOSS_MAX_CODE = 16        # box code columns
+POINT_LOSS_PART = 3             # intra-object part columns
+POINT_LOSS_TABLE = ("point_loss_cls", "point_loss_part", "point_loss_box", "point_loss", "point_pos_num")
+
+
+def point_loss_workspace_bytes(n_rows: int) -> int:
+    nb = int(load().modest_point_loss_workspace_bytes(int(n_rows)))
+    if nb < 0:
+        check(nb, "modest_point_loss_workspace_bytes")
+    return nb
+
+
+def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Optional[torch.Tensor] = None,
+               part_labels: Optional[torch.Tensor] = None, box_preds: Optional[torch.Tensor] = None,
+               box_labels: Optional[torch.Tensor] = None, code_weights: Optional[torch.Tensor] = None, *,
+               beta: float = 1.0 / 9.0, cls_weight: float = 1.0, part_weight: float = 1.0, box_weight: float = 1.0,
+               want_grad: bool = True, workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_point_loss on PyTorch's current stream: enqueue only, nothing is read back.
+    cls_preds (N, C) or (B, n, C) logits, part_preds (.., 3) with part_labels, box_preds (.., code) with box_labels and
+    code_weights (code): float32 device tensors; a term whose tensors are None is absent.  Predictions and their labels are
+    flattened to rows (a copy only where the strides demand one); labels (N elements) int32 or int64, contiguous.  The scalars
+    are rounded to float32, as torch rounds a Python scalar that meets a float32 tensor.
+    -> (table (5) float32 [point_loss_cls, point_loss_part, point_loss_box, point_loss, point_pos_num], grads): grads is None
+    without want_grad, else (grad_cls (N, C), grad_part (N, 3) or None, grad_box (N, code) or None), d point_loss / d
+    prediction, every element written.  `out` = (table, grad_cls, grad_part, grad_box) supplies the buffers (None where no
+    buffer is due)."""
+    with_part, with_box = part_preds is not None, box_preds is not None
+    if with_part != (part_labels is not None):
+        raise ValueError("part_preds and part_labels come together")
+    if with_box != (box_labels is not None) or with_box != (code_weights is not None):
+        raise ValueError("box_preds, box_labels and code_weights come together")
+    named = (("cls_preds", cls_preds), ("labels", labels), ("part_preds", part_preds), ("part_labels", part_labels),
+             ("box_preds", box_preds), ("box_labels", box_labels), ("code_weights", code_weights))
+    for name, t in named:
+        if t is None and name not in ("cls_preds", "labels"):
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if name == "labels":
+            if t.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"labels must be int32 or int64, got {t.dtype}")
+        elif t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    dev = cls_preds.device
+    if cls_preds.ndim < 2:
+        raise ValueError(f"cls_preds {tuple(cls_preds.shape)} must be (N, num_class) or (B, n, num_class)")
+    K = int(cls_preds.shape[-1])
+    if K < 1 or K > POINT_LOSS_MAX_CLASS:
+        raise ValueError(f"num_class = {K} is outside the limit of 1 .. {POINT_LOSS_MAX_CLASS} class columns")
+    N = int(labels.numel())
+    if N > POINT_LOSS_MAX_ROWS:
+        raise ValueError(f"labels has {N} rows, above the limit of {POINT_LOSS_MAX_ROWS} rows per call")
+    if cls_preds.numel() != N * K:
+        raise ValueError(f"cls_preds has {cls_preds.numel()} elements, expected {N} rows of {K} classes")
+    code = 0
+    if with_box:
+        if box_preds.ndim < 2:
+            raise ValueError(f"box_preds {tuple(box_preds.shape)} must be (N, code) or (B, n, code)")
+        code = int(box_preds.shape[-1])
+        if code < 1 or code > POINT_LOSS_MAX_CODE:
+            raise ValueError(f"code size = {code} is outside the limit of 1 .. {POINT_LOSS_MAX_CODE} box columns")
+        for name, t in (("box_preds", box_preds), ("box_labels", box_labels)):
+            if t.numel() != N * code:
+                raise ValueError(f"{name} has {t.numel()} elements, expected {N} rows of code size {code}")
+        if tuple(code_weights.shape) != (code,) or not code_weights.is_contiguous():
+            raise ValueError(f"code_weights {tuple(code_weights.shape)} must be a contiguous (code,) = ({code},)")
+    if with_part:
+        for name, t in (("part_preds", part_preds), ("part_labels", part_labels)):
+            if t.numel() != N * POINT_LOSS_PART:
+                raise ValueError(f"{name} has {t.numel()} elements, expected {N} rows of {POINT_LOSS_PART} columns")
+    for name, t in named[1:]:
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, cls_preds on {dev}")
+    rows = lambda t, c: t.reshape(-1, c).contiguous() if t is not None else None      # noqa: E731
+    cls, labels = rows(cls_preds, K), labels.reshape(-1).contiguous()
+    part, part_t = rows(part_preds, POINT_LOSS_PART), rows(part_labels, POINT_LOSS_PART)
+    box, box_t = rows(box_preds, max(code, 1)), rows(box_labels, max(code, 1))
+    want = (("table", (5,), True), ("grad_cls", (N, K), want_grad), ("grad_part", (N, POINT_LOSS_PART), want_grad and with_part),
+            ("grad_box", (N, code), want_grad and with_box))
+    if out is None:
+        out = [torch.empty(shape, dtype=torch.float32, device=dev) if need else None for _, shape, need in want]
+    if len(out) != 4:
+        raise ValueError("out must be (table, grad_cls, grad_part, grad_box)")
+    for t, (name, shape, need) in zip(out, want):
+        if (t is not None) != need:
+            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
+        if t is not None:
+            _dev(t, torch.float32, f"out {name}")
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
+    table, gcls, gpart, gbox = out
+    nbytes = point_loss_workspace_bytes(N)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    _dev(workspace, torch.uint8, "workspace")
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        check(load().modest_point_loss(N, K, code, ptr(cls), ptr(labels), int(labels.dtype == torch.int64), ptr(part), ptr(part_t),
+                                       ptr(box), ptr(box_t), ptr(code_weights), float(beta), float(cls_weight), float(part_weight),
+                                       float(box_weight), ptr(gcls), ptr(gpart), ptr(gbox), ptr(table), workspace.data_ptr(),
+                                       workspace.numel(), _stream()), "modest_point_loss")
+    return table, ((gcls, gpart, gbox) if want_grad else None)
+
+
+def point_loss_backward(grads, upstream: torch.Tensor):
+    """modest_point_loss_backward on PyTorch's current stream: the gradient buffers of `point_loss` (grad_part and grad_box
+    may be None) times the float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
+    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("upstream must be a float32 device tensor of one element")
+    if len(grads) != 3:
+        raise ValueError("grads must be (grad_cls, grad_part, grad_box)")
+    for g in grads:
+        if g is not None:
+            _dev(g, torch.float32, "a gradient buffer")
+            if g.device != upstream.device:
+                raise ValueError("the gradient buffers and upstream are on different devices")
+    gcls, gpart, gbox = grads
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    num = lambda t: int(t.numel()) if t is not None else 0       # noqa: E731
+    with torch.cuda.device(upstream.device):
+        check(load().modest_point_loss_backward(num(gcls), num(gpart), num(gbox), ptr(gcls), ptr(gpart), ptr(gbox),
+                                                upstream.data_ptr(), _stream()), "modest_point_loss_backward")
+    return grads

@@ -59,6 +59,12 @@ the RoI heads with its gradients in one call -- on ``RoIH
 ``pcdet.models.roi_heads.roi_head_template``, imported for it if it is not yet; a head that overrides
 ``get_box_reg_layer_loss`` or ``get_box_cls_layer_loss`` reaches the method that was replaced, and a head class with a
 ``get_loss`` of its own (``SECONDHead``) keeps it.
+
+``bind_point_loss()``, a function of its own like the others, sets ``modest_amd.utils.point_head_loss.get_loss`` -- the loss
+of the point heads with its gradients in one call -- on ``PointHeadBox``, ``PointHeadSimple`` and
+``PointIntraPartOffsetHead`` of ``pcdet.models.dense_heads``, whose modules are imported for it if they are not yet (each
+class defines its own ``get_loss``, so binding the template would do nothing); a head that overrides
+``get_cls_layer_loss``, ``get_part_layer_loss`` or ``get_box_layer_loss`` reaches the method that was replaced.
 """
 import importlib
 import importlib.util
@@ -96,6 +102,10 @@ ANCHOR_LOSS_NAME = "pcdet.models.dense_heads.anchor_head_template"
 ANCHOR_LOSS = "modest_amd.utils.anchor_head_loss"      # its method set on AnchorHeadTemplate by bind_anchor_loss()
 ROI_LOSS_NAME = PROPOSAL_LAYER_NAME
 ROI_LOSS = "modest_amd.utils.roi_head_loss"            # its method set on RoIHeadTemplate by bind_roi_loss()
+POINT_LOSS_NAMES = {"pcdet.models.dense_heads.point_head_box": "PointHeadBox",
+                    "pcdet.models.dense_heads.point_head_simple": "PointHeadSimple",
+                    "pcdet.models.dense_heads.point_intra_part_head": "PointIntraPartOffsetHead"}
+POINT_LOSS = "modest_amd.utils.point_head_loss"        # its method set on the three classes by bind_point_loss()
 
 
 class StandIn(types.ModuleType):
@@ -277,6 +287,31 @@ def bind_roi_loss():
         return None
     importlib.import_module(ROI_LOSS).bind(head)
     return mod
+
+
+def bind_point_loss():
+    """PointHeadBox / PointHeadSimple / PointIntraPartOffsetHead .get_loss := modest_amd.utils.point_head_loss.get_loss -- the
+    loss of the point heads with its gradients -- in the reference's modules where they are imported
+    or can be -> {module name: module} of the modules bound, or None where pcdet cannot be imported.  A function of its own:
+    install() and what it returns stay as they are.  Each class defines its own get_loss, so the three classes are bound,
+    not their template; the method each had is kept: a head that overrides get_cls_layer_loss, get_part_layer_loss or
+    get_box_layer_loss is handed to it.  A module that lacks its class is skipped.  Idempotent; before or after
+    ``import pcdet.models``; touches no GPU state."""
+    bound, found = {}, False
+    for name, cls_name in POINT_LOSS_NAMES.items():
+        mod = sys.modules.get(name)
+        if mod is None:
+            try:
+                mod = importlib.import_module(name)
+            except ImportError:
+                continue      # no pcdet on the path (or one that does not import here): nothing to bind onto
+        found = True
+        head = getattr(mod, cls_name, None)
+        if head is None:
+            continue
+        importlib.import_module(POINT_LOSS).bind(head)
+        bound[name] = mod
+    return bound if found else None
 
 
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
