@@ -129,7 +129,10 @@ __global__ __launch_bounds__(AL_T) void al_loss(LossParams p) {
                 const float v = p.l1 ? nrm : (quad ? ((0.5f * (nrm * nrm)) / p.beta) : (nrm - p.half_beta));
                 sum_loc = sum_loc + v * wr;
                 if (gb) {
-                    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : gl;
+                    // where() hands the branch not taken a zero and pow's backward multiplies it by 2 n: +0 for a finite n (gl + 0 is
+                    // gl), a NaN for an infinite or NaN one, as autograd gives it
+                    const float dead = ((0.f / p.beta) * 0.5f) * (2.f * nrm);
+                    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : (p.l1 ? gl : gl + dead);
                     const float g_d = (g_n * sign_f32(d)) * p.cw[k];
                     const float g_t = replaced ? 0.f : -g_d;               // where(isnan): no gradient to the replaced target
                     const float g_in = replaced ? g_d + (-g_d) : g_d;      // ... its share goes to the input and cancels

@@ -96,7 +96,10 @@ __device__ __forceinline__ float sl1_col(const RoiLossParams &p, int k, float in
     const float nrm = fabsf(d);
     const bool quad = !p.l1 && nrm < p.beta;
     const float v = p.l1 ? nrm : (quad ? ((0.5f * (nrm * nrm)) / p.beta) : (nrm - p.half_beta));
-    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : gl;
+    // where() hands the branch not taken a zero and pow's backward multiplies it by 2 n: +0 for a finite n (gl + 0 is
+    // gl), a NaN for an infinite or NaN one, as autograd gives it
+    const float dead = ((0.f / p.beta) * 0.5f) * (2.f * nrm);
+    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : (p.l1 ? gl : gl + dead);
     const float g_d = (g_n * sign_f32(d)) * cw;
     *grad = replaced ? g_d + (-g_d) : g_d;    // where(isnan): the target's share goes to the input and cancels
     return v;
@@ -190,7 +193,9 @@ __global__ __launch_bounds__(RL_T) void rl_loss(RoiLossParams p) {
                     const bool quad = m < 1.f;
                     csum = csum + (quad ? 0.5f * (m * m) : m - 0.5f);
                     if (gr) {
-                        const float g_m = (quad ? (g_c * 0.5f) * (2.f * m) : g_c) * sign_f32(m);
+                        // the same smooth L1 (beta = 1): where()'s zero for the branch not taken, times 2 m
+                        const float dead = 0.f * (2.f * m);
+                        const float g_m = (quad ? (g_c * 0.5f) * (2.f * m) : g_c + dead) * sign_f32(m);
                         const float g_h = na == nb ? g_m / 2.f : g_m;          // min of two equal values: half to each side
                         const float ga = na > nb ? 0.f : g_h, gb = na < nb ? 0.f : g_h;
                         // the norm of a zero vector hands on 0

@@ -2,6 +2,7 @@
 csrc/anchor_loss.hip, as configs of tests/anchor_loss_seq.py (not a test module; tests/test_anchor_loss_cpu.py runs them
 through the restatement and exact(), tests/test_gpu_anchor_loss.py through the kernels)."""
 from anchor_loss_seq import base_cfg as c
+from anchor_loss_seq import edge_scene_cfgs
 
 CASES = {
     # N one row short of, at, one past and four times the workgroup (256), and below one
@@ -33,4 +34,15 @@ CASES = {
     "int64": c(B=2, N=257, int64=True, seed=120, pos=0.1),
     "label_above": c(B=1, N=257, seed=121, specials=["label_above"]),
     "label_above_int64": c(B=1, N=257, int64=True, label_max=9, seed=122, pos=0.1),
+    # labels no 32-bit cast keeps: 2^32 + 1 (truncated: class 1), 2^31, -2^40 and INT64_MIN (truncated: background 0); int32 -7
+    "labels_wide": c(B=1, N=257, int64=True, seed=126, specials=["labels_wide"]),
+    "labels_wide_int32": c(B=1, N=257, seed=127, specials=["labels_wide"]),
 }
+# headings at every bin edge, saturating and infinite direction logits, non-finite and huge values, the head's real layout:
+# then al_finish past one row of 256 partials and past its first batch of 8 rows: the configs of the recorded
+# tests/golden/anchor_loss_edges.npz
+CASES.update(edge_scene_cfgs())
+# the cases that may hold a NaN, and the outputs that hold it: no other output of these and no output of another case does
+MAY_HOLD_NAN = {"nan6": ("losses", "grad_box"), "dir_logits": ("losses", "grad_dir"),
+                "nonfinite": ("losses", "grad_cls", "grad_box"), "nonfinite_inf": ("grad_box",),
+                "nonfinite_l1": ("losses", "grad_box")}

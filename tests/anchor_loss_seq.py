@@ -16,7 +16,8 @@ A config is a plain dict (what the fixture records as JSON):
     B, N, num_class, code, bins (0: no direction head), beta, dir_offset, cls_weight, loc_weight, dir_weight, code_weights,
     seed, samples (per sample "mixed" | "none" | "all" | "ignore"), pos (fraction of positives in a mixed sample),
     label_max (labels are drawn from 1 .. label_max), int64 (labels), specials (names of ``SPECIALS`` written over the seeded
-    draw, each at a fixed positive anchor of sample 0)
+    draw, each at a fixed positive anchor of sample 0), layout (optional (H, W): the head's real layout, three anchor tensors
+    of two rotations each and predictions shaped (B, H, W, 6 * columns))
 """
 import json
 
@@ -26,6 +27,7 @@ F = np.float32
 U = 2.0 ** -24           # half an ulp, relative: one float32 rounding
 TINY = 2.0 ** -149       # ... and absolute, where a product underflows
 FUNC_U = 2 * U           # one ulp: the budget of a transcendental
+FLT_MAX = float(np.finfo(np.float32).max)
 T = 256                  # anchors of a workgroup
 ALPHA, GAMMA = 0.25, 2.0
 OUTPUTS = ("losses", "grad_cls", "grad_box", "grad_dir")
@@ -44,9 +46,13 @@ class Bounded:
     def of(x):
         return x if isinstance(x, Bounded) else Bounded(np.asarray(x, dtype=np.float64))
 
-    def _rounded(self, v, carried, product=False):
+    def _rounded(self, v, carried, product=False, definite=None):
+        """the operation's own rounding on top of what its operands hand on.  An infinite value whose sign cannot be another
+        (`definite`: an infinity plus something finite, a product or quotient of operands that cannot cross 0) is that
+        infinity in float32 as well: bound 0"""
         with np.errstate(invalid="ignore", over="ignore"):
-            return Bounded(v, carried + U * (np.abs(v) + carried) + (TINY if product else 0.0))
+            e = carried + U * (np.abs(v) + carried) + (TINY if product else 0.0)
+            return Bounded(v, np.where(np.isinf(v) & (np.isfinite(carried) if definite is None else definite), 0.0, e))
 
     def __add__(self, o):
         o = Bounded.of(o)
@@ -66,7 +72,10 @@ class Bounded:
     def __mul__(self, o):
         o = Bounded.of(o)
         with np.errstate(invalid="ignore", over="ignore"):
-            return self._rounded(self.v * o.v, np.abs(self.v) * o.e + np.abs(o.v) * self.e + self.e * o.e, True)
+            v = self.v * o.v
+            carried = np.abs(self.v) * o.e + np.abs(o.v) * self.e + self.e * o.e
+            carried = np.where(np.isnan(carried) & ~np.isnan(v), np.inf, carried)      # 0 times an unbounded factor: unbounded
+            return self._rounded(v, carried, True, (np.abs(self.v) > self.e) & (np.abs(o.v) > o.e))
     __rmul__ = __mul__
 
     def __truediv__(self, o):
@@ -76,7 +85,7 @@ class Bounded:
             room = np.abs(o.v) - o.e
             carried = np.where(room > 0, (self.e + np.abs(v) * o.e) / np.where(room > 0, room, 1.0), np.inf)
             carried = np.where((self.e == 0) & (o.e == 0), 0.0, carried)
-            return self._rounded(v, carried, True)
+            return self._rounded(v, carried, True, (np.abs(self.v) > self.e) & (np.abs(o.v) > o.e))
 
     def __rtruediv__(self, o):
         return Bounded.of(o) / self
@@ -106,7 +115,8 @@ def _exp(x):
     with np.errstate(over="ignore", invalid="ignore"):
         v = np.exp(x.v)
         carried = np.where(x.e > 0, np.exp(x.v + x.e) - v, 0.0)
-        return Bounded(v, carried + FUNC_U * (v + carried) + TINY)
+        # past float64's range (and float32's long before): the same infinity on both sides
+        return Bounded(v, np.where(np.isinf(v) & np.isfinite(x.e), 0.0, carried + FUNC_U * (v + carried) + TINY))
 
 
 def _log(x, fn=np.log, low=0.0):
@@ -116,7 +126,7 @@ def _log(x, fn=np.log, low=0.0):
         v = fn(x.v)
         ok = x.v - x.e > low
         carried = np.where(x.e > 0, np.where(ok, v - fn(np.where(ok, x.v - x.e, 1.0)), np.inf), 0.0)
-        return Bounded(v, carried + FUNC_U * (np.abs(v) + carried) + TINY)
+        return Bounded(v, np.where(np.isposinf(x.v) & np.isfinite(x.e), 0.0, carried + FUNC_U * (np.abs(v) + carried) + TINY))
 
 
 def _log1p(x):
@@ -173,9 +183,9 @@ def _group_tree(x):
     return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
 
 
-def tree_sum(lanes):
+def tree_sum(lanes, rows_read=None):
     """(B, N) float32 lane values -> float32: al_loss's workgroup sums, then al_finish (lane t adds partials t, t + 256, ..
-    in ascending order, then the same tree)"""
+    in ascending order, then the same tree).  `rows_read` mis-states al_finish on purpose: only that many rows of 256"""
     B, N = lanes.shape
     blocks = (N + T - 1) // T
     pad = np.zeros((B, blocks * T), dtype=F)
@@ -186,7 +196,7 @@ def tree_sum(lanes):
         grid = np.zeros((rows * T,), dtype=F)
         grid[:part.size] = part
         acc = np.zeros((T,), dtype=F)
-        for r in grid.reshape(rows, T):
+        for r in grid.reshape(rows, T)[:rows_read]:
             acc = acc + r
         return _group_tree(acc)
 
@@ -197,13 +207,14 @@ def tree_depth(B, N, lane_adds):
     return lane_adds + 8 + (B * blocks + T - 1) // T + 8
 
 
-def _total(lanes, B, N, lane_adds):
+def _total(lanes, B, N, lane_adds, rows_read=None):
     if not _is_b(lanes):
-        return tree_sum(lanes)
+        return tree_sum(lanes, rows_read)
     with np.errstate(invalid="ignore"):
         v = lanes.v.sum(dtype=np.float64)
         carried = lanes.e.sum(dtype=np.float64)
-        return Bounded(v, carried + tree_depth(B, N, lane_adds) * U * (np.abs(lanes.v).sum(dtype=np.float64) + carried))
+        e = carried + tree_depth(B, N, lane_adds) * U * (np.abs(lanes.v).sum(dtype=np.float64) + carried)
+        return Bounded(v, np.where(np.isinf(v) & np.isfinite(carried), 0.0, e))      # infinities of one sign among finite terms
 
 
 # ---- the statement ---------------------------------------------------------------------------------------------------------
@@ -221,8 +232,15 @@ def decisions(inp, cfg):
     return _evaluate(inp, cfg, None)[1]
 
 
-def _evaluate(inp, cfg, dec):
-    """dec None: float32 (the restatement) -> (outputs, decisions); else float64 with bounds along `dec`"""
+FAULTS = ("trunc_period", "no_upper_clamp", "no_dead_share", "finish_256", "finish_2048")
+
+
+def _evaluate(inp, cfg, dec, faults=()):
+    """dec None: float32 (the restatement) -> (outputs, decisions); else float64 with bounds along `dec`.  `faults` (names of
+    FAULTS) mis-states the contract on purpose: truncation instead of floor in limit_period, no upper clamp of the bin, the
+    smooth-L1 gradient without the dead branch's share, al_finish reading only its first 256 / 2048 partials"""
+    assert set(faults) <= set(FAULTS), faults
+    rows_read = 1 if "finish_256" in faults else (8 if "finish_2048" in faults else None)
     f32 = dec is None
     S = scalars32(cfg)
     wrap = (lambda a: np.asarray(a, dtype=F)) if f32 else (lambda a: Bounded(np.asarray(a, dtype=np.float64)))
@@ -258,10 +276,10 @@ def _evaluate(inp, cfg, dec):
         pt = _where(tmask, oms, s)                                                   # t (1 - s) + (1 - t) s: one term is 0
         fw = const(aw) * (pt * pt) if not f32 else aw * (pt * pt)
         e = _exp(-_abs(x))
-        xt = x32 * t if f32 else _mask(x, tmask)                                     # x * t
+        xt = x32 * t if f32 else _where(np.isinf(x32) & ~tmask, Bounded(np.full((), np.nan)), _mask(x, tmask))     # x * t: inf * 0
         relu = _mask(x, x32 > 0) if not f32 else np.maximum(x32, F(0))
         bce = (relu - xt) + _log1p(e)
-        sum_cls = _total(lane_sum((fw[..., c] * bce[..., c]) * wc for c in range(C)), B, N, C)
+        sum_cls = _total(lane_sum((fw[..., c] * bce[..., c]) * wc for c in range(C)), B, N, C, rows_read)
         gw = (g_cls * wc)[..., None]
         g_fw, g_bce = gw * bce, gw * fw
         c1 = _mask(g_bce, x32 >= 0)
@@ -299,9 +317,21 @@ def _evaluate(inp, cfg, dec):
             v = nrm
         else:
             v = _where(quad, (half_c * (nrm * nrm)) / beta, nrm - half)
-        sum_loc = _total(lane_sum(_mask(v[..., k] * wr, pos) for k in range(code)), B, N, code)
+        sum_loc = _total(lane_sum(_mask(v[..., k] * wr, pos) for k in range(code)), B, N, code, rows_read)
         gl = (g_loc * wr)[..., None]
-        g_n = gl if S["l1"] else _where(quad, ((gl / beta) * half_c) * (two_c * nrm), gl)
+        if S["l1"]:
+            g_n = gl
+        else:
+            # where() hands the branch not taken a zero, and pow's backward multiplies it by 2 n: +0 for a finite n, a NaN
+            # for an infinite or NaN one.  The quadratic side's zero goes through a subtraction only and stays a zero
+            if f32:
+                dead = ((np.zeros((B, N, 1), dtype=F) / beta) * half_c) * (two_c * nrm)
+                d["dead_nan"] = np.isnan(dead) & ("no_dead_share" not in faults)
+                dead = np.where(d["dead_nan"], dead, F(0))
+                linear = gl + dead
+            else:      # gl + (+0) is gl, exactly: the share is a float32 decision, not an operation with a rounding
+                linear = _where(d["dead_nan"], Bounded(np.full((), np.nan)), gl)
+            g_n = _where(quad, ((gl / beta) * half_c) * (two_c * nrm), linear)
         g_d = _scale(g_n, sign_d) * cw
         g_t = _mask(-g_d, ~replaced)
         g_in = _where(replaced, g_d + (-g_d), g_d)
@@ -318,9 +348,10 @@ def _evaluate(inp, cfg, dec):
             if f32:
                 rot = np.asarray(inp["tg"], dtype=F)[..., 6] + np.asarray(inp["anchors"], dtype=F)[None, :, 6]
                 val = rot - S["dir_offset"]
-                lim = val - np.floor(val / S["two_pi"] + F(0)) * S["two_pi"]
+                lim = val - (np.trunc if "trunc_period" in faults else np.floor)(val / S["two_pi"] + F(0)) * S["two_pi"]
                 fl = np.floor(lim / S["bin_width"])
-                b_ = np.where(~(fl >= 0), F(0), np.where(fl >= F(bins - 1), F(bins - 1), fl)).astype(np.int64)
+                top = F(np.inf) if "no_upper_clamp" in faults else F(bins - 1)      # unclamped: a bin that is no column
+                b_ = np.where(~(fl >= 0), F(0), np.where(fl >= top, top, np.minimum(fl, F(bins)))).astype(np.int64)
                 d["bin"] = np.where(pos, b_, 0)
             bin_ = d["bin"]
             m = z32.max(axis=-1, keepdims=True)                                      # a selection: exact
@@ -330,13 +361,13 @@ def _evaluate(inp, cfg, dec):
             onehot = np.arange(bins)[None, None, :] == bin_[..., None]
             if f32:
                 lsm = zm - lse[..., None]
-                picked = np.take_along_axis(lsm, bin_[..., None], axis=-1)[..., 0]
+                picked = np.take_along_axis(lsm, np.minimum(bin_, bins - 1)[..., None], axis=-1)[..., 0]
             else:
                 lsm = zm - Bounded(lse.v[..., None], lse.e[..., None])
-                picked = Bounded(np.take_along_axis(lsm.v, bin_[..., None], axis=-1)[..., 0],
-                                 np.take_along_axis(lsm.e, bin_[..., None], axis=-1)[..., 0])
+                picked = Bounded(np.take_along_axis(lsm.v, np.minimum(bin_, bins - 1)[..., None], axis=-1)[..., 0],
+                                 np.take_along_axis(lsm.e, np.minimum(bin_, bins - 1)[..., None], axis=-1)[..., 0])
             lane_dir = _mask((-picked) * wr, pos)
-            sum_dir = _total(lane_dir, B, N, 0)
+            sum_dir = _total(lane_dir, B, N, 0, rows_read)
             g = (-(g_dir * wr))[..., None]
             prob = _exp(lsm)
             out["grad_dir"] = _mask(_mask(g, onehot) - prob * g, pos[..., None])
@@ -359,9 +390,9 @@ def _evaluate(inp, cfg, dec):
     return out, d
 
 
-def restate(inp, cfg):
+def restate(inp, cfg, faults=()):
     """the kernel's float32 results: {"losses" (4), "grad_cls", "grad_box", "grad_dir" (with a direction head)}"""
-    return _evaluate(inp, cfg, None)[0]
+    return _evaluate(inp, cfg, None, faults)[0]
 
 
 def exact(inp, cfg, dec=None):
@@ -377,6 +408,19 @@ def _where3(name, idx):
     return "(sample %d, anchor %d, column %d)" % tuple(int(v) for v in idx)
 
 
+def error_over_bound(g, v, e):
+    """float32 results g against exact()'s (v, e) -> (|g - v| / e per element, where v is a NaN, where g is one).  A NaN
+    bound counts as a NaN value.  A value past float32's range even after its bound is that infinity in float32: equal
+    infinities agree, anything else there is infinitely far off"""
+    nan_v, nan_g = np.isnan(v) | np.isnan(e), np.isnan(g)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        over = ~nan_v & (np.abs(v) - e > FLT_MAX)
+        same_inf = over & np.isinf(g) & (np.sign(g) == np.sign(v))
+        err = np.where(nan_v | nan_g | same_inf, 0.0, np.where(over, np.inf, np.abs(g - np.where(nan_v | same_inf, 0.0, v))))
+        ratio = np.where(err == 0, 0.0, np.where(e > 0, err / np.where(e > 0, e, 1.0), np.inf))
+    return ratio, nan_v, nan_g
+
+
 def bound_report(got, ex, what="ours"):
     """every element of every output against exact(): |got - value| <= bound, a NaN exactly where the value is one.
     -> (text naming (sample, anchor, column) of each output's worst miss, or "", {output: largest error / bound})"""
@@ -389,10 +433,7 @@ def bound_report(got, ex, what="ours"):
         if g.shape != v.shape:
             lines.append(f"{what} {name}: shape {g.shape}, expected {v.shape}")
             continue
-        nan_v, nan_g = np.isnan(v) | np.isnan(e), np.isnan(g)
-        err = np.where(nan_v | nan_g, 0.0, np.abs(g - np.where(nan_v, 0.0, v)))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(err == 0, 0.0, np.where(e > 0, err / np.where(e > 0, e, 1.0), np.inf))
+        ratio, nan_v, nan_g = error_over_bound(g, v, e)
         ratios[name] = float(ratio.max()) if ratio.size else 0.0
         bad = (ratio > 1.0) | (nan_v != nan_g)
         if bad.any():
@@ -490,7 +531,114 @@ def _sp_label_above(inp, cfg, rows):
     inp["labels"][0, rows[9]] = cfg["num_class"] + 5
 
 
-SPECIALS = {"logits": _sp_logits, "beta": _sp_beta, "nan2": _sp_nan2, "nan6": _sp_nan6, "label_above": _sp_label_above}
+def edge_headings(bins, dir_offset):
+    """float32 headings at and around every bin edge: j * bin_width and j * bin_width + dir_offset for j in [-2 bins, 3 bins],
+    each computed in float32 and in float64 rounded once, each with its +-1, +-2, +-3 float32 neighbours; then +-0, +-1e-30,
+    -1e-7 (lim rounds to 2 pi: only the upper clamp keeps the bin in range), +-50, +-1e4, 3e38.  -> (L,) float32, the
+    -1e-7 entry at index L - 6"""
+    bw32, bw64, off32 = F(2 * np.pi / bins), 2 * np.pi / bins, F(dir_offset)
+    base = []
+    for j in range(-2 * bins, 3 * bins + 1):
+        base += [F(j) * bw32, F(j) * bw32 + off32, F(j * bw64), F(j * bw64 + float(dir_offset))]
+    out = []
+    for v in base:
+        lo = hi = F(v)
+        near = [F(v)]
+        for _ in range(3):
+            lo, hi = np.nextafter(lo, F(-np.inf)), np.nextafter(hi, F(np.inf))
+            near += [lo, hi]
+        out += near
+    out = sorted(set(float(v) for v in out))
+    return np.array(out + [0.0, -0.0, 1e-30, -1e-30, -1e-7, 50.0, -50.0, 1e4, -1e4, 3e38], dtype=F)
+
+
+def edge_shape(bins, dir_offset, most=600):
+    """(B, N) that hold every edge heading twice (an anchor of heading 0, then one of 1.57), N even and at most `most`"""
+    need = 2 * len(edge_headings(bins, dir_offset))
+    B = -(-need // most)
+    N = -(-need // B)
+    return B, N + N % 2
+
+
+def _sp_dir_edges(inp, cfg, rows):
+    """every anchor positive (samples "all"); the edge headings over the anchors in order, each on an anchor of heading 0 and
+    on its neighbour of heading 1.57, the rest +0; ONE row of direction logits for all (the scene is about the bin)"""
+    h = np.repeat(edge_headings(int(cfg["bins"]), cfg["dir_offset"]), 2)
+    flat = np.zeros(inp["tg"].shape[:2], dtype=F).reshape(-1)
+    assert h.size <= flat.size and inp["tg"].shape[1] % 2 == 0 and (inp["labels"] > 0).all()
+    flat[:h.size] = h
+    inp["tg"][..., 6] = flat.reshape(inp["tg"].shape[:2])
+    inp["dir"][...] = inp["dir"][0, 0].copy()
+
+
+def _sp_dir_logits(inp, cfg, rows):
+    """direction logits that saturate, tie, overflow exp's argument and are infinite, on positives (2 bins)"""
+    for j, z in enumerate(([100.0, -100.0], [0.0, 0.0], [-0.0, 0.0], [88.8, -88.8], [1e30, -1e30], [np.inf, 0.0])):
+        inp["dir"][0, rows[j], :2] = np.array(z, dtype=F)
+
+
+def _sp_nonfinite_box(inp, cfg, rows, vals=(np.nan, np.inf, -np.inf), col6=True):
+    """NaN, +inf, -inf in box column 1 of three positives and in column 6 of three others; inf in a target's column 1 and in
+    another target's column 6"""
+    for j, v in enumerate(vals):
+        inp["box"][0, rows[j], 1] = F(v)
+        if col6:
+            inp["box"][0, rows[3 + j], 6] = F(v)
+    inp["tg"][0, rows[6], 1] = F(np.inf)
+    if col6:
+        inp["tg"][0, rows[7], 6] = F(np.inf)
+
+
+def _sp_inf_box(inp, cfg, rows):
+    """infinities alone, outside the heading column (sin of an infinity is a NaN): rpn_loss_loc is +inf, not a NaN"""
+    _sp_nonfinite_box(inp, cfg, rows, vals=(np.inf, -np.inf), col6=False)
+
+
+def _sp_nonfinite_cls(inp, cfg, rows):
+    """inf, -inf and NaN in a class logit: of a positive (the target column and another) and of a background anchor"""
+    back = np.flatnonzero(inp["labels"][0] == 0)
+    for j, v in enumerate((np.inf, -np.inf, np.nan)):
+        inp["cls"][0, rows[8 + j], 0] = F(v)
+        inp["cls"][0, rows[11 + j], -1] = F(v)
+        inp["cls"][0, back[j], 0] = F(v)
+
+
+def _sp_extreme(inp, cfg, rows):
+    """finite and huge: class logits +-88.9 (exp(88.9) is past float32) and +-1e30 on positives and a background anchor, box
+    values 1e20 and -1e30, headings 1e10 and -3e38 in a prediction and in a target"""
+    back = np.flatnonzero(inp["labels"][0] == 0)
+    for j, v in enumerate((88.9, -88.9, 1e30, -1e30)):
+        inp["cls"][0, rows[j], :] = F(v)
+        inp["cls"][0, rows[j], 0] = F(-v)
+        inp["cls"][0, back[j], :] = F(v)
+    inp["box"][0, rows[4], 0] = F(1e20)
+    inp["box"][0, rows[5], 2] = F(-1e30)
+    inp["tg"][0, rows[6], 3] = F(1e20)
+    inp["box"][0, rows[7], 6] = F(1e10)
+    inp["box"][0, rows[8], 6] = F(-3e38)
+    inp["tg"][0, rows[9], 6] = F(1e10)
+    inp["tg"][0, rows[10], 6] = F(-3e38)
+
+
+def _sp_labels_wide(inp, cfg, rows):
+    """int64 labels that a truncating cast would change: 2^32 + 1 (to class 1), 2^31 (to a negative label), -2^40 and
+    INT64_MIN (to 0: background instead of ignored); int32: -7, ignored as -1 is"""
+    if inp["labels"].dtype == np.int64:
+        for j, v in enumerate((2 ** 32 + 1, 2 ** 31, -2 ** 40, -2 ** 63)):
+            inp["labels"][0, rows[j]] = v
+    else:
+        inp["labels"][0, rows[0]] = -7
+    for r in rows[:4]:
+        if inp["labels"][0, r] <= 0:
+            inp["tg"][0, r] = 0
+
+
+SPECIALS = {"logits": _sp_logits, "beta": _sp_beta, "nan2": _sp_nan2, "nan6": _sp_nan6, "label_above": _sp_label_above,
+            "dir_edges": _sp_dir_edges, "dir_logits": _sp_dir_logits, "nonfinite_box": _sp_nonfinite_box, "inf_box": _sp_inf_box,
+            "nonfinite_cls": _sp_nonfinite_cls, "extreme": _sp_extreme, "labels_wide": _sp_labels_wide}
+WHOLE_SCENE = ("dir_edges",)     # specials that lay out every anchor themselves: no fixed positives are written first
+LAYOUT_ROT = ((0.0, 1.57), (0.5, 2.2), (-1.0, 3.0))      # a layout's three anchor tensors: two rotations each
+LAYOUT_SIZE = ((3.9, 1.6, 1.56), (0.8, 0.6, 1.73), (1.76, 0.6, 1.73))
 
 
 def make_inputs(cfg):
@@ -513,7 +661,8 @@ def make_inputs(cfg):
             labels[b] = -1
         else:
             raise ValueError(mode)
-    if cfg["specials"]:
+    fixed = [n for n in cfg["specials"] if n not in WHOLE_SCENE]
+    if fixed:
         labels[0, :40:3] = 1 + np.arange(len(labels[0, :40:3])) % int(cfg["label_max"])     # enough positives, at fixed places
         labels[0, 1:40:3] = 0
     tg = (rs.standard_normal((B, N, code)) * 0.5).astype(F)
@@ -523,13 +672,43 @@ def make_inputs(cfg):
     anchors[:, :3] = (rs.uniform(-40, 40, size=(N, 3))).astype(F)
     anchors[:, 3:6] = F(1.6)
     anchors[:, 6] = np.where(np.arange(N) % 2 == 0, F(0), F(1.57))
+    if cfg.get("layout"):      # (H, W): three anchor tensors (1, H, W, 1, 2, code), flattened as the reference's cat(dim=-3)
+        H, W = cfg["layout"]
+        assert N == H * W * 6
+        grid = anchors.reshape(H, W, 3, 2, code)
+        for a in range(3):
+            grid[:, :, a, :, 3:6] = np.asarray(LAYOUT_SIZE[a], dtype=F)
+            grid[:, :, a, :, 6] = np.asarray(LAYOUT_ROT[a], dtype=F)
     inp.update(labels=labels.astype(np.int64 if cfg["int64"] else np.int32), tg=tg, anchors=anchors,
                cw=np.asarray(cfg["code_weights"], dtype=F))
     if cfg["specials"]:
-        rows = _first_positives(inp, 10)
+        rows = _first_positives(inp, 10 if fixed else 1)
         for name in cfg["specials"]:
             SPECIALS[name](inp, cfg, rows)
     return inp
+
+
+def edge_scene_cfgs():
+    """the second config set: what tools/make_golden_anchor_loss.py records into tests/golden/anchor_loss_edges.npz and
+    tests/anchor_loss_cases.py runs as cases.  A direction scene records the scalars and grad_dir alone ("record")"""
+    c, out = base_cfg, {}
+    for bins, off in ((2, 0.78539), (3, 0.3), (4, 0.0), (8, 0.78539), (1, 0.0)):
+        B, N = edge_shape(bins, off)
+        out[f"dir_edges_b{bins}"] = c(B=B, N=N, num_class=1, bins=bins, dir_offset=off, samples=["all"] * B, seed=30 + bins,
+                                      specials=["dir_edges"], record=["losses", "grad_dir"])
+    out["dir_logits"] = c(B=1, N=70, seed=41, specials=["dir_logits"], record=["losses", "grad_dir"])
+    out["nonfinite"] = c(B=1, N=70, seed=42, specials=["nonfinite_box", "nonfinite_cls"])
+    out["nonfinite_inf"] = c(B=1, N=70, seed=43, specials=["inf_box"])
+    out["nonfinite_l1"] = c(B=1, N=70, seed=44, beta=0.0, specials=["nonfinite_box"])
+    out["extreme"] = c(B=1, N=70, seed=45, specials=["extreme"])
+    out["layout"] = c(B=2, N=36, seed=46, pos=0.5, layout=[2, 3])
+    # al_finish past its first row of 256 partials (257 of them), past it with one partial a sample (2049 samples of one
+    # anchor, with and without a positive), and past its first batch of 8 rows inside a sample (9 samples of 229 workgroups:
+    # 2061 partials, sample 1 holds partial 256 and sample 8 partial 2048).  Only the four scalars are recorded
+    out["parts257"] = c(B=1, N=65537, seed=47, pos=0.01, record=["losses"])
+    out["parts_b2049"] = c(B=2049, N=1, seed=48, pos=0.5, record=["losses"])
+    out["parts2061"] = c(B=9, N=58369, seed=49, pos=0.002, record=["losses"])
+    return out
 
 
 # ---- the fixture -------------------------------------------------------------------------------------------------------------
@@ -541,6 +720,18 @@ def scenes(gold):
 def recorded(gold, name):
     out = {k: gold[f"{name}/{k}"] for k in OUTPUTS if f"{name}/{k}" in gold}
     return out
+
+
+def only(outputs, rec):
+    """the outputs (restated, or exact()'s pairs) that a scene recorded"""
+    return {k: v for k, v in outputs.items() if k in rec}
+
+
+def anchor_tensors(cfg, flat, order=(0, 1, 2)):
+    """the three (1, H, W, 1, 2, code) anchor tensors of a layout whose cat(dim=-3), in `order`, flattens to `flat`"""
+    H, W = cfg["layout"]
+    grid = np.asarray(flat).reshape(1, H, W, 3, 2, -1)
+    return [np.ascontiguousarray(grid[:, :, :, a:a + 1]) for a in order]
 
 
 # ---- a bare head: the attributes get_loss reads ---------------------------------------------------------------------------
@@ -578,6 +769,12 @@ def bare_head(cfg, inp, device="cpu", head_class=None, requires_grad=True):
     head.num_class, head.num_anchors_per_location, head.use_multihead = int(cfg["num_class"]), 1, False
     a = torch.from_numpy(inp["anchors"].copy()).to(device)
     head.anchors = [a.view(1, 1, -1, 1, 1, a.shape[-1])]
+    shape = lambda k: inp[k].shape       # noqa: E731
+    if cfg.get("layout"):
+        H, W = cfg["layout"]
+        head.num_anchors_per_location = 6
+        head.anchors = [torch.from_numpy(t).to(device) for t in anchor_tensors(cfg, inp["anchors"])]
+        shape = lambda k: (inp[k].shape[0], H, W, 6 * inp[k].shape[2])       # noqa: E731
     head.cls_loss_func = loss_stub("SigmoidFocalClassificationLoss", alpha=ALPHA, gamma=GAMMA)
     cw = torch.from_numpy(np.asarray(inp["cw"], dtype=F).copy()).to(device)
     if float(cfg["beta"]) == 0.0:
@@ -585,8 +782,8 @@ def bare_head(cfg, inp, device="cpu", head_class=None, requires_grad=True):
     else:
         head.reg_loss_func = loss_stub("WeightedSmoothL1Loss", beta=cfg["beta"], code_weights=cw)
     head.dir_loss_func = loss_stub("WeightedCrossEntropyLoss")
-    preds = {k: torch.from_numpy(inp[k].copy()).to(device).requires_grad_(requires_grad) for k in ("cls", "box", "dir")
-             if inp[k] is not None}
+    preds = {k: torch.from_numpy(inp[k].copy().reshape(shape(k))).to(device).requires_grad_(requires_grad)
+             for k in ("cls", "box", "dir") if inp[k] is not None}
     head.forward_ret_dict = dict(cls_preds=preds["cls"], box_preds=preds["box"],
                                  box_cls_labels=torch.from_numpy(inp["labels"].copy()).to(device),
                                  box_reg_targets=torch.from_numpy(inp["tg"].copy()).to(device))

@@ -2,6 +2,7 @@
 of csrc/point_loss.hip, as configs of tests/point_loss_seq.py (not a test module; tests/test_point_loss_cpu.py runs them through
 the restatement and exact(), tests/test_gpu_point_loss.py through the kernels)."""
 from point_loss_seq import EDGE, base_cfg as c
+from point_loss_seq import edge_scene_cfgs
 
 PART, BOX, SIMPLE = "PointIntraPartOffsetHead", "PointHeadBox", "PointHeadSimple"
 
@@ -43,3 +44,13 @@ CASES = {
     "outside": c(head=PART, B=2, N=130, num_class=3, seed=327, specials=["part_outside", "label_above", "nonfinite_off"]),
     "outside_c1": c(head=BOX, B=1, N=130, num_class=1, seed=328, specials=["label_above", "nonfinite_off"]),
 }
+# non-finite and huge values on positive rows: the configs of the recorded tests/golden/point_loss_edges.npz
+CASES.update(edge_scene_cfgs())
+# ... and what is not recorded: -88.9 against a part label above 0 (a float32 sigmoid evaluated as 1 / (1 + exp(-x)) is exactly 0
+# there, the contract's is not) and a NaN part logit (the reference's binary_cross_entropy raises)
+CASES["extreme_sigmoid"] = c(head=PART, B=1, N=130, num_class=3, seed=66, specials=["extreme"])
+CASES["nan_part"] = c(head=PART, B=1, N=130, num_class=3, seed=67, specials=["nan_part"])
+# the cases that may hold a NaN, and the outputs that hold it: no other output of these and no output of another case does
+MAY_HOLD_NAN = {"nonfinite": ("table", "grad_cls", "grad_box"), "nonfinite_inf": ("grad_box",), "nonfinite_l1": ("table",),
+                "extreme": ("grad_box",), "extreme_box": ("grad_box",), "extreme_sigmoid": ("grad_box",),
+                "nan_part": ("table", "grad_part")}

@@ -22,12 +22,14 @@ import json
 import numpy as np
 
 from anchor_loss_seq import (FUNC_U, U, Bounded, F, _abs, _exp, _is_b, _log, _log1p, _mask, _scale, _sigmoid, _total,  # noqa: F401
-                             _where, tree_depth, tree_sum)      # U, tree_sum, tree_depth: for the modules that import this one
+                             _where, error_over_bound, tree_depth, tree_sum)      # U, tree_sum, tree_depth: for the modules that import this one
 
 OUTPUTS = ("table", "grad_cls", "grad_part", "grad_box")
 TABLE = ("point_loss_cls", "point_loss_part", "point_loss_box", "point_loss", "point_pos_num")
 FAULTS = ("count_per_sample", "part_divisor_without_3", "ignored_rows_weighted", "target_at_label", "box_for_background",
           "part_grad_off_positives")
+NO_DEAD_SHARE = "no_dead_share"      # one more fault, shown on the recorded non-finite scene: the smooth-L1 gradient without the
+#                                      zero that where() hands the branch not taken
 ALPHA, GAMMA = 0.25, 2.0
 HEADS = ("PointHeadBox", "PointIntraPartOffsetHead", "PointHeadSimple")
 
@@ -113,7 +115,7 @@ def _evaluate(inp, cfg, dec, faults=()):
         pt = _where(tmask, oms, s)                                                     # t (1 - s) + (1 - t) s: one term is 0
         fw = (aw if f32 else Bounded(aw.astype(np.float64))) * (pt * pt)
         e = _exp(-_abs(x))
-        xt = x32 * t if f32 else _mask(x, tmask)                                       # x * t
+        xt = x32 * t if f32 else _where(np.isinf(x32) & ~tmask, Bounded(np.full((), np.nan)), _mask(x, tmask))       # x * t: inf * 0
         relu = np.maximum(x32, F(0)) if f32 else _mask(x, x32 > 0)
         bce = (relu - xt) + _log1p(e)
         lane_cls = zero
@@ -171,7 +173,10 @@ def _evaluate(inp, cfg, dec, faults=()):
             if S["l1"]:
                 g_n = gl * (np.ones(nrm.shape, dtype=F) if f32 else Bounded(np.ones(nrm.v.shape)))
             else:
-                g_n = _where(quad, ((gl / beta) * const(0.5)) * (const(2) * nrm), gl)
+                # where() hands the branch not taken a zero and pow's backward multiplies it by 2 n: +0 for a finite n (gl + 0
+                # is gl, exactly: a float32 decision, no rounding), a NaN for an infinite or NaN one
+                dead_nan = D("dead_nan", lambda: np.isnan(((F(0) / beta) * F(0.5)) * (F(2) * nrm)) & (NO_DEAD_SHARE not in faults))
+                g_n = _where(quad, ((gl / beta) * const(0.5)) * (const(2) * nrm), _where(dead_nan, const(np.nan), gl))
             g_d = _scale(g_n, sign_d) * cw
             g_in = _where(replaced, g_d + (-g_d), g_d)
             out["grad_box"] = _mask(g_in, box_rows[:, None])
@@ -227,10 +232,7 @@ def bound_report(got, ex, what="ours"):
         if g.shape != v.shape:
             lines.append(f"{what} {name}: shape {g.shape}, expected {v.shape}")
             continue
-        nan_v, nan_g = np.isnan(v) | np.isnan(e), np.isnan(g)
-        err = np.where(nan_v | nan_g, 0.0, np.abs(g - np.where(nan_v, 0.0, v)))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(err == 0, 0.0, np.where(e > 0, err / np.where(e > 0, e, 1.0), np.inf))
+        ratio, nan_v, nan_g = error_over_bound(g, v, e)
         ratios[name] = float(ratio.max()) if ratio.size else 0.0
         bad = (ratio >= 1.0) | (nan_v != nan_g)
         if bad.any():
@@ -367,7 +369,68 @@ def _sp_nonfinite_off(inp, cfg, rows):
             inp[key][b, 1] = -F(np.inf)
 
 
-SPECIALS = {"logits": _sp_logits, "part": _sp_part, "part_recorded": _sp_part_recorded, "beta": _sp_beta, "nan": _sp_nan,
+def _sp_nonfinite_box(inp, cfg, rows, vals=(np.nan, np.inf, -np.inf)):
+    """on positive rows: NaN, +inf, -inf in a box prediction's column 1, inf in a box label's column 1"""
+    if "box" in inp:
+        for j, v in enumerate(vals):
+            inp["box"][rows[26 + j], 1] = F(v)
+        inp["box_t"][rows[29], 1] = F(np.inf)
+
+
+def _sp_inf_box(inp, cfg, rows):
+    """infinities alone: point_loss_box is +inf, not a NaN"""
+    _sp_nonfinite_box(inp, cfg, rows, vals=(np.inf, -np.inf))
+
+
+def _sp_nonfinite_cls(inp, cfg, rows):
+    """inf, -inf and NaN in a focal logit: of a positive (the first and the last class column) and of a background row"""
+    for j, v in enumerate((np.inf, -np.inf, np.nan)):
+        inp["cls"][rows[30 + j], 0] = F(v)
+        inp["cls"][rows[33 + j], -1] = F(v)
+        inp["cls"][rows[30 + j] + 1, 0] = F(v)
+
+
+def _sp_inf_part(inp, cfg, rows):
+    """inf and -inf in a part logit of a positive row, against part labels of 0, 1 and 0.5"""
+    if "part" in inp:
+        for j, v in enumerate((np.inf, -np.inf)):
+            inp["part"][rows[36 + j], :] = F(v)
+            inp["part_t"][rows[36 + j], :] = np.array(PART_LABELS, dtype=F)
+
+
+def _sp_nan_part(inp, cfg, rows):
+    """a NaN part logit of a positive row: the reference's binary_cross_entropy raises on the CPU (its input is not within
+    [0, 1]), so this is a case against the restatement, not a recorded one"""
+    if "part" in inp:
+        inp["part"][rows[38], 1] = F(np.nan)
+
+
+def _sp_extreme(inp, cfg, rows, recorded=False):
+    """finite and huge, on positive rows: focal logits +-88.9 (exp(88.9) is past float32) and +-1e30, also on background rows;
+    part logits of the same values against part labels 0, 1 and 0.5; box values 1e20 and -1e30, a box label of 1e20, and one
+    value of -3e38 (one, so that no float32 sum overflows where the exact one does not).  `recorded`: -88.9 against part
+    labels of 0 alone, the point of ``_sp_part`` (a float32 sigmoid evaluated as 1 / (1 + exp(-x)) is exactly 0 there)"""
+    for j, v in enumerate((88.9, -88.9, 1e30, -1e30)):
+        inp["cls"][rows[26 + j], :] = F(v)
+        inp["cls"][rows[26 + j], 0] = F(-v)
+        inp["cls"][rows[26 + j] + 1, :] = F(v)
+        if "part" in inp:
+            inp["part"][rows[30 + j], :] = F(v)
+            inp["part_t"][rows[30 + j], :] = F(0) if recorded and v == -88.9 else np.array(PART_LABELS, dtype=F)
+    if "box" in inp:
+        inp["box"][rows[34], 0] = F(1e20)
+        inp["box"][rows[35], 2] = F(-1e30)
+        inp["box_t"][rows[36], 3] = F(1e20)
+        inp["box"][rows[37], 4] = F(-3e38)
+
+
+def _sp_extreme_recorded(inp, cfg, rows):
+    _sp_extreme(inp, cfg, rows, recorded=True)
+
+
+SPECIALS = {"nonfinite_box": _sp_nonfinite_box, "inf_box": _sp_inf_box, "nonfinite_cls": _sp_nonfinite_cls, "inf_part": _sp_inf_part,
+            "nan_part": _sp_nan_part, "extreme": _sp_extreme, "extreme_recorded": _sp_extreme_recorded,
+            "logits": _sp_logits, "part": _sp_part, "part_recorded": _sp_part_recorded, "beta": _sp_beta, "nan": _sp_nan,
             "part_outside": _sp_part_outside, "label_above": _sp_label_above, "nonfinite_off": _sp_nonfinite_off}
 EDGE = ["logits", "part", "beta", "nan"]                      # the `edge` case
 EDGE_RECORDED = ["logits", "part_recorded", "beta", "nan"]    # what the recorded `edge` scene holds
@@ -412,6 +475,18 @@ def make_inputs(cfg):
     for name in cfg["specials"]:
         SPECIALS[name](inp, cfg, SPECIAL_ROWS)
     return inp
+
+
+def edge_scene_cfgs():
+    """the second config set: what tools/make_golden_point_loss.py records into tests/golden/point_loss_edges.npz and
+    tests/point_loss_cases.py runs as cases: non-finite and huge values on positive rows"""
+    c = base_cfg
+    box, part, simple = HEADS
+    return {"nonfinite": c(head=part, B=1, N=130, num_class=3, seed=61, specials=["nonfinite_box", "nonfinite_cls", "inf_part"]),
+            "nonfinite_inf": c(head=box, B=1, N=130, seed=62, specials=["inf_box"]),
+            "nonfinite_l1": c(head=box, B=1, N=130, seed=63, beta=0.0, specials=["nonfinite_box"]),
+            "extreme": c(head=part, B=1, N=130, num_class=3, seed=64, specials=["extreme_recorded"]),
+            "extreme_box": c(head=box, B=1, N=130, seed=65, specials=["extreme_recorded"])}
 
 
 # ---- the fixture -------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 of csrc/roi_loss.hip, as configs of tests/roi_loss_seq.py (not a test module; tests/test_roi_loss_cpu.py runs them through the
 restatement and exact(), tests/test_gpu_roi_loss.py through the kernels)."""
 from roi_loss_seq import EDGE, base_cfg as c
+from roi_loss_seq import edge_scene_cfgs
 
 CASES = {
     # R = 1, around a wavefront (64), around the workgroup (256) and four workgroups and a bit
@@ -39,3 +40,14 @@ CASES = {
     "strided": c(B=2, M=130, gt_cols=8, seed=226),
     "strided_code9": c(B=1, M=130, code=9, gt_cols=12, seed=227, code_weights=[1.0] * 7 + [0.5, 0.25]),
 }
+# non-finite and huge values on foreground rows, with and without the corner term: the configs of the recorded
+# tests/golden/roi_loss_edges.npz
+CASES.update(edge_scene_cfgs())
+# ... and what is not recorded: -88.9 against a label of 1 (a float32 sigmoid evaluated as 1 / (1 + exp(-x)) is exactly 0 there,
+# the contract's is not) and a NaN logit (the reference's binary_cross_entropy raises)
+CASES["extreme_sigmoid"] = c(B=1, M=130, seed=57, corner=False, specials=["extreme"])
+CASES["nan_cls"] = c(B=1, M=130, seed=58, specials=["nan_cls"])
+# the cases that may hold a NaN, and the outputs that hold it: no other output of these and no output of another case does
+MAY_HOLD_NAN = {"nonfinite": ("table", "grad_reg"), "nonfinite_inf": ("grad_reg",), "nonfinite_l1": ("table",),
+                "nonfinite_corner": ("table", "grad_reg"), "extreme": ("grad_reg",), "extreme_corner": ("grad_reg",),
+                "extreme_sigmoid": ("grad_reg",), "nan_cls": ("table", "grad_cls")}

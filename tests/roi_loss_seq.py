@@ -23,11 +23,13 @@ import json
 import numpy as np
 
 from anchor_loss_seq import (FUNC_U, U, Bounded, F, _abs, _exp, _is_b, _log, _log1p, _mask, _scale, _sigmoid, _total,  # noqa: F401
-                             _trig, _where, tree_sum)      # U and tree_sum: for the modules that import this one
+                             _trig, _where, error_over_bound, tree_sum)      # U and tree_sum: for the modules that import this one
 
 OUTPUTS = ("table", "grad_cls", "grad_reg")
 TABLE = ("rcnn_loss_cls", "rcnn_loss_reg", "rcnn_loss_corner", "rcnn_loss", "fg_sum", "cls_valid")
 FAULTS = ("decode_clamps_roi", "flip_by_2pi", "tie_to_first", "reg_reports_corner", "zero_norm_divides", "corner_on_extra")
+NO_DEAD_SHARE = "no_dead_share"      # one more fault, shown on the recorded non-finite scene: the smooth-L1 gradient without the
+#                                      zero that where() hands the branch not taken
 # the 8 corners of boxes_to_corners_3d: the template's signs, times 0.5
 SIGN_X = (1, 1, -1, -1, 1, 1, -1, -1)
 SIGN_Y = (1, -1, -1, 1, 1, -1, -1, 1)
@@ -139,9 +141,13 @@ def _evaluate(inp, cfg, dec, faults=()):
         lane_reg = _mask(lane_reg, fg)
         sum_reg = _total(lane_reg.reshape(1, R) if f32 else Bounded(lane_reg.v.reshape(1, R), lane_reg.e.reshape(1, R)), 1, R, code)
         gl = const(S["w_reg"]) / den_f
-        g_n = gl if S["l1"] else _where(quad, ((gl / beta) * const(0.5)) * (const(2) * nrm), gl)
         if S["l1"]:
-            g_n = g_n * (np.ones(nrm.shape, dtype=F) if f32 else Bounded(np.ones(nrm.v.shape)))
+            g_n = gl * (np.ones(nrm.shape, dtype=F) if f32 else Bounded(np.ones(nrm.v.shape)))
+        else:
+            # where() hands the branch not taken a zero and pow's backward multiplies it by 2 n: +0 for a finite n (gl + 0 is
+            # gl, exactly: a float32 decision, no rounding), a NaN for an infinite or NaN one
+            dead_nan = D("dead_nan", lambda: np.isnan(((F(0) / beta) * F(0.5)) * (F(2) * nrm)) & (NO_DEAD_SHARE not in faults))
+            g_n = _where(quad, ((gl / beta) * const(0.5)) * (const(2) * nrm), _where(dead_nan, const(np.nan), gl))
         cwr = cw[None, :] if f32 else Bounded(cw.v[None, :], cw.e[None, :])
         g_d = _scale(g_n, sign_d) * cwr
         g_in = _where(replaced, g_d + (-g_d), g_d)
@@ -177,11 +183,17 @@ def _evaluate(inp, cfg, dec, faults=()):
                 ax_, ay_, az_ = PX - GX, PY - GY, PZ - GZ
                 bx_, by_ = PX - FX, PY - FY
                 na, nb = _sqrt(dot3(ax_, ay_, az_)), _sqrt(dot3(bx_, by_, az_))
+                # a squared distance past float32's range is an infinite norm in float32: a branch float32 decides
+                na = _where(D(f"na_inf{k}", lambda: np.isposinf(na)), const(np.inf), na)
+                nb = _where(D(f"nb_inf{k}", lambda: np.isposinf(nb)), const(np.inf), nb)
                 second = D(f"second{k}", lambda: nb < na)
                 m = _where(second, nb, na)
                 cquad = D(f"cquad{k}", lambda: m < F(1))
                 csum = csum + _where(cquad, const(0.5) * (m * m), m - const(0.5))
-                g_m = _scale(_where(cquad, (g_c * const(0.5)) * (const(2) * m), g_c), D(f"sign_m{k}", lambda: _sign(m)))
+                # the corner distances go through the same smooth L1 (beta = 1): the same zero from where() times 2 m
+                cdead = D(f"cdead{k}", lambda: np.isnan(F(0) * (F(2) * m)) & (NO_DEAD_SHARE not in faults))
+                g_m = _scale(_where(cquad, (g_c * const(0.5)) * (const(2) * m), _where(cdead, const(np.nan), g_c)),
+                             D(f"sign_m{k}", lambda: _sign(m)))
                 tie = D(f"tie{k}", lambda: na == nb)
                 g_h = g_m if "tie_to_first" in faults else _where(tie, g_m / const(2), g_m)
                 first_less = D(f"first_less{k}", lambda: na < nb)
@@ -257,10 +269,7 @@ def bound_report(got, ex, what="ours"):
         if g.shape != v.shape:
             lines.append(f"{what} {name}: shape {g.shape}, expected {v.shape}")
             continue
-        nan_v, nan_g = np.isnan(v) | np.isnan(e), np.isnan(g)
-        err = np.where(nan_v | nan_g, 0.0, np.abs(g - np.where(nan_v, 0.0, v)))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            ratio = np.where(err == 0, 0.0, np.where(e > 0, err / np.where(e > 0, e, 1.0), np.inf))
+        ratio, nan_v, nan_g = error_over_bound(g, v, e)
         ratios[name] = float(ratio.max()) if ratio.size else 0.0
         bad = (ratio > 1.0) | (nan_v != nan_g)
         if bad.any():
@@ -390,7 +399,58 @@ def _sp_mask_values(inp, cfg, rows):
     inp["mask"][rows[9]] = -1
 
 
-SPECIALS = {"logits": _sp_logits, "logits_recorded": _sp_logits_recorded, "beta": _sp_beta, "zero_distance": _sp_zero_distance, "sizes": _sp_sizes, "nan": _sp_nan,
+def _sp_nonfinite(inp, cfg, rows):
+    """on foreground rows: NaN, +inf, -inf in rcnn_reg's column 1 and in its column 6; inf in a gt's column 1 and in another
+    gt's column 6 (the encoded targets are those infinities)"""
+    for j, v in enumerate((np.nan, np.inf, -np.inf)):
+        inp["reg"][rows[10 + j], 1] = F(v)
+        inp["reg"][rows[13 + j], 6] = F(v)
+    inp["gt"][rows[16], 1] = F(np.inf)
+    inp["gt"][rows[17], 6] = F(np.inf)
+
+
+def _sp_inf_reg(inp, cfg, rows):
+    """infinities alone: rcnn_loss_reg is +inf, not a NaN"""
+    inp["reg"][rows[10], 1], inp["reg"][rows[11], 2], inp["gt"][rows[12], 0] = F(np.inf), F(-np.inf), F(np.inf)
+
+
+def _sp_nonfinite_cls(inp, cfg, rows, vals=(np.inf, -np.inf)):
+    """inf and -inf in rcnn_cls, on rows that are not foreground, against labels of 0 and 1"""
+    for j, v in enumerate(vals * 2):
+        inp["cls"][rows[20 + j] + 1] = F(v)
+        inp["labels"][rows[20 + j] + 1] = j // len(vals)
+
+
+def _sp_nan_cls(inp, cfg, rows):
+    """a NaN in rcnn_cls: the reference's binary_cross_entropy raises on the CPU (its input is not within [0, 1]), so this
+    is a case against the restatement, not a recorded one"""
+    _sp_nonfinite_cls(inp, cfg, rows, vals=(np.nan,))
+
+
+def _sp_extreme(inp, cfg, rows, recorded=False):
+    """finite and huge: logits +-88.9 (exp(88.9) is past float32) and +-1e30 against labels 0 and 1, rcnn_reg values 1e20 and
+    -1e30, a gt centre of 1e20, and (without the corner term, where column 6 is a plain difference) headings 1e10 in a gt
+    and -3e38 in rcnn_reg -- one value of that size, so that no float32 sum overflows where the exact one does not.
+    `recorded`: without -88.9 against label 1, the point of ``_sp_logits`` (a float32 sigmoid evaluated as 1 / (1 + exp(-x))
+    is exactly 0 there, the contract's is 2.4e-39)"""
+    for j, v in enumerate((88.9, -88.9, 1e30, -1e30) * 2):
+        if not (recorded and j == 5):
+            inp["cls"][rows[20 + j] + 1] = F(v)
+        inp["labels"][rows[20 + j] + 1] = j // 4
+    inp["reg"][rows[10], 0] = F(1e20)
+    inp["reg"][rows[11], 2] = F(-1e30)
+    inp["gt"][rows[16], 0] = F(1e20)
+    if not cfg["corner"]:
+        inp["reg"][rows[13], 6] = F(-3e38)
+        inp["gt"][rows[14], 6] = F(1e10)
+
+
+def _sp_extreme_recorded(inp, cfg, rows):
+    _sp_extreme(inp, cfg, rows, recorded=True)
+
+
+SPECIALS = {"nonfinite": _sp_nonfinite, "inf_reg": _sp_inf_reg, "nonfinite_cls": _sp_nonfinite_cls, "nan_cls": _sp_nan_cls, "extreme": _sp_extreme, "extreme_recorded": _sp_extreme_recorded,
+            "logits": _sp_logits, "logits_recorded": _sp_logits_recorded, "beta": _sp_beta, "zero_distance": _sp_zero_distance, "sizes": _sp_sizes, "nan": _sp_nan,
             "headings": _sp_headings, "tie": _sp_tie, "mask_values": _sp_mask_values}
 EDGE = ["logits", "beta", "zero_distance", "sizes", "nan", "headings"]      # the `edge` case
 EDGE_RECORDED = ["logits_recorded"] + EDGE[1:]                              # what the recorded `edge` scene holds
@@ -447,6 +507,18 @@ def make_inputs(cfg):
         for name in cfg["specials"]:
             SPECIALS[name](inp, cfg, rows)
     return inp
+
+
+def edge_scene_cfgs():
+    """the second config set: what tools/make_golden_roi_loss.py records into tests/golden/roi_loss_edges.npz and
+    tests/roi_loss_cases.py runs as cases: non-finite and huge values on foreground rows, with and without the corner term"""
+    c = base_cfg
+    return {"nonfinite": c(B=1, M=130, seed=51, corner=False, specials=["nonfinite", "nonfinite_cls"]),
+            "nonfinite_inf": c(B=1, M=130, seed=52, corner=False, specials=["inf_reg"]),
+            "nonfinite_l1": c(B=1, M=130, seed=53, corner=False, beta=0.0, specials=["nonfinite"]),
+            "nonfinite_corner": c(B=1, M=130, seed=54, specials=["nonfinite"]),
+            "extreme": c(B=1, M=130, seed=55, corner=False, specials=["extreme_recorded"]),
+            "extreme_corner": c(B=1, M=130, seed=56, specials=["extreme_recorded"])}
 
 
 # ---- the fixture -------------------------------------------------------------------------------------------------------------

@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 import anchor_loss_seq as seq
-from anchor_loss_cases import CASES
+from anchor_loss_cases import CASES, MAY_HOLD_NAN
 
 F = np.float32
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_loss.npz")
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_loss_edges.npz")
 
 
 @pytest.fixture(scope="module")
@@ -123,11 +124,16 @@ def test_the_comparison_is_not_vacuous(evaluated):
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
-def test_edge_cases_through_the_restatement(name):
+def test_edge_cases_through_the_restatement(name, edge_evaluated):
     cfg = CASES[name]
-    inp = seq.make_inputs(cfg)
-    ours, dec = seq._evaluate(inp, cfg, None)
-    why, ratios = seq.bound_report(ours, seq.exact(inp, cfg, dec))
+    if name in edge_evaluated:      # a recorded config: evaluated once
+        cfg, inp, ours, dec, ex, _ = edge_evaluated[name]
+        assert cfg == CASES[name]
+    else:
+        inp = seq.make_inputs(cfg)
+        ours, dec = seq._evaluate(inp, cfg, None)
+        ex = seq.exact(inp, cfg, dec)
+    why, ratios = seq.bound_report(ours, ex)
     assert not why, why
     pos = inp["labels"] > 0
     assert (ours["grad_box"][~pos] == 0).all() and (ours["grad_cls"][inp["labels"] < 0] == 0).all()
@@ -138,10 +144,25 @@ def test_edge_cases_through_the_restatement(name):
         assert above.any() and (ours["grad_box"][above] != 0).any()
         t_grad = ours["grad_cls"][above]                 # no class column is the target: every column pushes down
         assert (t_grad >= 0).all()
+    # a NaN only in the named outputs of the named cases
+    for k, v in ours.items():
+        assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
     if name == "nan6":
         assert np.isnan(ours["losses"][3])
-    else:
-        assert not any(np.isnan(v).any() for v in ours.values())
+    if name == "nonfinite_inf":      # infinities alone: +inf in the scalars, as exact() has it; a NaN in three gradient elements
+        assert np.isposinf(ours["losses"][[1, 3]]).all() and np.isnan(ours["grad_box"]).sum() == 3
+    if name.startswith("labels_wide"):
+        rows = np.arange(0, 40, 3)                       # the fixed positives of a config with specials
+        lab = inp["labels"][0, rows[:4]].astype(np.int64)
+        if cfg["int64"]:
+            assert lab.tolist() == [2 ** 32 + 1, 2 ** 31, -2 ** 40, -2 ** 63]
+            # 2^32 + 1 and 2^31 are labels above num_class (positives without a target column), the negative ones are ignored
+            assert (ours["grad_box"][0, rows[:2]] != 0).any(axis=-1).all() and (ours["grad_cls"][0, rows[:2]] > 0).all()
+            assert (ours["grad_cls"][0, rows[2:4]] == 0).all() and (ours["grad_box"][0, rows[2:4]] == 0).all()
+        else:
+            assert lab[0] == -7 and (ours["grad_cls"][0, rows[0]] == 0).all() and (ours["grad_box"][0, rows[0]] == 0).all()
+    if name == "parts_b2049":
+        assert set(np.unique(dec["count"]).tolist()) == {0, 1}
 
 
 def test_tree_sum_is_the_written_tree():
@@ -172,6 +193,179 @@ def test_tree_sum_is_the_written_tree():
     assert got == (w[0] + w[1]) + (w[2] + w[3])
     assert abs(float(got) - lanes.astype(np.float64).sum()) <= seq.tree_depth(3, 1040, 0) * seq.U * lanes.sum()
     assert seq.tree_depth(4, 321408, 3) == 3 + 8 + 20 + 8
+    # 2061 partials (9 samples of 229 workgroups): al_finish's lane t adds partials t, t + 256, .. in ascending order, nine rows
+    # of them, the last of 13; written with Python loops over the partials of a cheap sum (one value a workgroup)
+    B, blocks = 9, 229
+    lanes = np.zeros((B, blocks * 256 - 255), dtype=F)                      # N = 58369: the last workgroup holds one anchor
+    lanes[:, ::256] = rs.uniform(0, 1, size=(B, blocks)).astype(F)          # one non-zero lane a workgroup: its partial
+    part = lanes[:, ::256].reshape(-1)
+    assert part.size == 2061
+    acc = [F(0)] * 256
+    for j in range(part.size):
+        acc[j % 256] = acc[j % 256] + part[j]
+    w = []
+    for q in range(4):
+        v = np.array(acc[q * 64:(q + 1) * 64], dtype=F)
+        for off in (32, 16, 8, 4, 2, 1):
+            v = v + v[np.arange(64) ^ off]
+        w.append(v[0])
+    want = (w[0] + w[1]) + (w[2] + w[3])
+    assert seq.tree_sum(lanes) == want
+    # ... and a reader of only the first row, or only the first 8 rows, gives another sum
+    assert seq.tree_sum(lanes, rows_read=1) != want and seq.tree_sum(lanes, rows_read=8) != want
+    assert seq.tree_sum(lanes, rows_read=9) == want and seq.tree_depth(9, 58369, 0) == 8 + 9 + 8
+
+
+# ------------------------------------------------------------------------------------------------ the recorded edge scenes
+@pytest.fixture(scope="module")
+def edges():
+    return dict(np.load(EDGES))
+
+
+@pytest.fixture(scope="module")
+def edge_evaluated(edges):
+    """per edge scene (cfg, inputs, restatement, decisions, exact, recorded): computed once, left unchanged"""
+    out = {}
+    for name, cfg in seq.scenes(edges):
+        inp = seq.make_inputs(cfg)
+        ours, dec = seq._evaluate(inp, cfg, None)
+        out[name] = (cfg, inp, ours, dec, seq.exact(inp, cfg, dec), seq.recorded(edges, name))
+    return out
+
+
+def scene_mismatch(cfg, inp, ours, dec, rec, ex=None):
+    """the comparison of a recorded scene -> text, "" when everything agrees: the recorded values and ours within the bound
+    of exact() along ours' decisions with NaNs at the same places, the zero patterns, and the direction bin read off the
+    one negative element of each recorded grad_dir row"""
+    ex = seq.exact(inp, cfg, dec) if ex is None else ex
+    lines = [seq.bound_report(seq.only(ours, rec), seq.only(ex, rec), "ours")[0],
+             seq.bound_report(rec, seq.only(ex, rec), "the reference")[0], seq.zero_report(seq.only(ours, rec), rec)]
+    pos = inp["labels"] > 0
+    if "grad_dir" in rec and cfg["bins"] > 1:
+        rows = pos & ((rec["grad_dir"] < 0).sum(axis=-1) == 1)
+        if not rows[pos].all() and "dir_logits" not in cfg["specials"]:      # a saturated softmax leaves 0 in the target's bin
+            lines.append("a recorded grad_dir row without exactly one negative element")
+        differ = rows & (np.argmin(rec["grad_dir"], axis=-1) != dec["bin"])
+        if differ.any():
+            b, i = np.argwhere(differ)[0]
+            lines.append(f"{int(differ.sum())} direction bins differ, the first at (sample {b}, anchor {i}): heading {inp['tg'][b, i, 6]!r}")
+    return "\n".join(line for line in lines if line)
+
+
+def test_edges_fixture_is_small_and_holds_the_case_configs(edges):
+    assert os.path.getsize(EDGES) <= 64 * 1024
+    cfgs = seq.edge_scene_cfgs()
+    assert [n for n, _ in seq.scenes(edges)] == list(cfgs)
+    for name, cfg in seq.scenes(edges):
+        assert cfg == json.loads(json.dumps(cfgs[name])) == json.loads(json.dumps(CASES[name])), name
+        rec = seq.recorded(edges, name)
+        assert set(rec) == set(cfg.get("record", seq.OUTPUTS)), name
+        assert cfg["N"] <= 600 or cfg["record"] == ["losses"]
+        assert rec["losses"].dtype == F and rec["losses"].shape == (4,)
+    assert {(c["bins"], c["dir_offset"]) for n, c in cfgs.items() if n.startswith("dir_edges")} == {
+        (2, 0.78539), (3, 0.3), (4, 0.0), (8, 0.78539), (1, 0.0)}
+    assert cfgs["nonfinite_l1"]["beta"] == 0.0 and cfgs["layout"]["layout"] == [2, 3]
+
+
+def test_edge_scenes_lie_within_the_derived_bound(edge_evaluated):
+    worst = {}
+    for name, (cfg, inp, ours, dec, ex, rec) in edge_evaluated.items():
+        why = scene_mismatch(cfg, inp, ours, dec, rec, ex)
+        assert not why, f"{name}\n{why}"
+        for v, e in ex.values():
+            assert not (np.isnan(e) & ~np.isnan(v)).any() and not (np.isinf(e) & np.isfinite(v)).any(), name      # a finite value, a finite bound
+        for who, got in (("ours", seq.only(ours, rec)), ("reference", rec)):
+            for k, v in seq.bound_report(got, seq.only(ex, rec), who)[1].items():
+                worst[(who, k)] = max(worst.get((who, k), 0.0), v)
+        for k, v in rec.items():
+            assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
+    print({f"{w} {k}": round(v, 3) for (w, k), v in sorted(worst.items())})
+    assert all(v <= 1.0 for v in worst.values())
+
+
+def test_direction_bins_at_their_edges(edge_evaluated):
+    for name, (cfg, inp, ours, dec, ex, rec) in edge_evaluated.items():
+        if not name.startswith("dir_edges"):
+            continue
+        bins, S = cfg["bins"], seq.scalars32(cfg)
+        assert (inp["labels"] > 0).all()
+        h = seq.edge_headings(bins, cfg["dir_offset"])
+        flat = inp["tg"][..., 6].reshape(-1)
+        assert np.array_equal(flat[:2 * h.size:2].view(np.uint32), h.view(np.uint32)) and np.array_equal(flat[:2 * h.size:2], flat[1:2 * h.size:2])
+        assert F(-1e-7) in h and F(3e38) in h and F(-50) in h and F(1e4) in h and np.signbit(h[h == 0]).any()
+        for j in (-2 * bins, -1, 1, 3 * bins):
+            e = F(j * (2 * np.pi / bins) + cfg["dir_offset"])
+            assert {e, np.nextafter(e, F(9e9)), np.nextafter(e, F(-9e9))} <= set(h.tolist())
+        bin_ = dec["bin"]
+        assert len(np.unique(bin_)) == bins                                  # every bin occurs
+        if bins == 1:
+            assert (rec["grad_dir"] == 0).all() and (ours["grad_dir"] == 0).all()      # softmax of one logit is 1
+            continue
+        assert ((rec["grad_dir"] < 0).sum(axis=-1) == 1).all() and np.array_equal(np.argmin(rec["grad_dir"], axis=-1), bin_), name
+        # a value just below 0 after the offset: lim rounds to 2 pi, the quotient to `bins`, and only the upper clamp keeps
+        # the index in range
+        val = (inp["tg"][..., 6] + inp["anchors"][None, :, 6]) - S["dir_offset"]
+        lim = val - np.floor(val / S["two_pi"] + F(0)) * S["two_pi"]
+        top = np.floor(lim / S["bin_width"]) >= bins
+        assert top.any() and (val[top] < 0).all() and (val[top] > -1e-6).all() and (bin_[top] == bins - 1).all(), name
+        if cfg["dir_offset"] == 0.0:
+            assert flat[2 * (h.size - 6)] == F(-1e-7) and top.reshape(-1)[2 * (h.size - 6)]
+        # negative and multi-period headings: truncation instead of floor would take another bin
+        assert (val < -S["two_pi"]).any() and (val > 2 * S["two_pi"]).any()
+
+
+def test_layout_scene_is_the_heads_real_layout(edge_evaluated):
+    import torch
+    cfg, inp, ours, dec, ex, rec = edge_evaluated["layout"]
+    tensors = seq.anchor_tensors(cfg, inp["anchors"])
+    assert len(tensors) == 3 and all(t.shape == (1, 2, 3, 1, 2, 7) for t in tensors)
+    assert len({tuple(t[0, 0, 0, 0, :, 3:].reshape(-1).tolist()) for t in tensors}) == 3      # distinct sizes and rotations
+    flat = torch.cat([torch.from_numpy(t) for t in tensors], dim=-3).reshape(-1, 7).numpy()    # as the reference flattens them
+    assert np.array_equal(flat, inp["anchors"])
+    head, preds = seq.bare_head(cfg, inp)
+    assert head.num_anchors_per_location == 6 and [tuple(p.shape) for p in preds.values()] == [(2, 2, 3, 18), (2, 2, 3, 42), (2, 2, 3, 12)]
+    # the wrapper's own flattening (the branch for several anchor tensors), without a device
+    from modest_amd.utils import anchor_head_loss
+    assert np.array_equal(anchor_head_loss._flat_anchors(head).numpy(), inp["anchors"])
+    assert anchor_head_loss._flat_anchors(head) is anchor_head_loss._flat_anchors(head)       # built once
+    # another order of concatenation changes at least one direction bin of a positive
+    pos = inp["labels"] > 0
+    for order in ((1, 0, 2), (2, 1, 0), (1, 2, 0)):
+        other = np.concatenate(seq.anchor_tensors(cfg, inp["anchors"], order), axis=-3).reshape(-1, 7)
+        assert (seq.decisions(dict(inp, anchors=other), cfg)["bin"] != dec["bin"])[pos].any(), order
+
+
+MUTATIONS = {"trunc_period": "dir_edges_b4", "no_upper_clamp": "dir_edges_b4", "no_dead_share": "nonfinite", "finish_256": "parts2061",
+             "finish_2048": "parts2061", "anchor order": "layout"}
+
+
+@pytest.mark.parametrize("fault", sorted(MUTATIONS))
+def test_each_mutation_fails_its_recorded_scene(edge_evaluated, fault):
+    cfg, inp, ours, dec, ex, rec = edge_evaluated[MUTATIONS[fault]]
+    assert not scene_mismatch(cfg, inp, ours, dec, rec, ex)
+    if fault == "anchor order":
+        inp = dict(inp, anchors=np.concatenate(seq.anchor_tensors(cfg, inp["anchors"], (1, 0, 2)), axis=-3).reshape(-1, 7))
+        bad, bad_dec = seq._evaluate(inp, cfg, None)
+    else:
+        assert fault in seq.FAULTS
+        bad, bad_dec = seq._evaluate(inp, cfg, None, (fault,))
+    why = scene_mismatch(cfg, inp, bad, bad_dec, rec, ex if fault.startswith("finish") else None)      # the sum decides no branch
+    assert why, fault
+    expected = {"trunc_period": "direction bins differ", "no_upper_clamp": "direction bins differ", "no_dead_share": "grad_box",
+                "finish_256": "losses", "finish_2048": "losses", "anchor order": "direction bins differ"}[fault]
+    assert expected in why, why
+    assert seq.report(bad, ours)                    # and the bit-for-bit comparison of the device tests sees it as well
+    if fault == "no_dead_share":
+        # the elements the share turns from finite to NaN: an infinite or NaN box value, or an infinite target, outside the
+        # heading column (there the sine is a NaN already), on a smooth-L1 head
+        rows = np.flatnonzero(inp["labels"][0] > 0)
+        turned = np.argwhere(np.isnan(ours["grad_box"]) & ~np.isnan(bad["grad_box"])).tolist()
+        assert turned == [[0, rows[0], 1], [0, rows[1], 1], [0, rows[2], 1], [0, rows[6], 1]]
+        assert np.array_equal(np.isnan(ours["grad_box"]), np.isnan(rec["grad_box"]))
+        assert bad["grad_box"][0, rows[0], 1] == 0 and abs(bad["grad_box"][0, rows[1], 1]) > 0
+        # with WeightedL1Loss there is no where(): nothing changes
+        cfg1, inp1, ours1, *_ = edge_evaluated["nonfinite_l1"]
+        assert not seq.report(seq.restate(inp1, cfg1, (fault,)), ours1)
 
 
 def test_scalars_round_to_float32_as_the_contract_says():

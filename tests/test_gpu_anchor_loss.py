@@ -18,6 +18,7 @@ from modest_amd.utils import anchor_head_loss as ahl
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_loss.npz")
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_loss_edges.npz")
 F = np.float32
 SENTINEL = 0x5A5A5A5A
 _restated = {}
@@ -26,6 +27,11 @@ _restated = {}
 @pytest.fixture(scope="module")
 def gold():
     return dict(np.load(GOLD))
+
+
+@pytest.fixture(scope="module")
+def edges():
+    return dict(np.load(EDGES))
 
 
 def restated(key, cfg):
@@ -47,9 +53,12 @@ def through_get_loss(cfg, inp, gpu, scale=None):
     assert loss.ndim == 0 and loss.is_cuda and loss.dtype == torch.float32 and loss.requires_grad
     assert all(type(v) is float for v in tb.values()) and ("rpn_loss_dir" in tb) == bool(cfg["bins"])
     (loss if scale is None else scale * loss).backward()
-    got = {"losses": losses_of(tb), "grad_cls": preds["cls"].grad.cpu().numpy(), "grad_box": preds["box"].grad.cpu().numpy()}
+    # a layout's predictions are (B, H, W, 6 * columns): their gradients come back in that shape
+    got = {"losses": losses_of(tb), "grad_cls": preds["cls"].grad.cpu().numpy().reshape(inp["cls"].shape),
+           "grad_box": preds["box"].grad.cpu().numpy().reshape(inp["box"].shape)}
     if "dir" in preds:
-        got["grad_dir"] = preds["dir"].grad.cpu().numpy()
+        assert preds["dir"].grad.shape == preds["dir"].shape
+        got["grad_dir"] = preds["dir"].grad.cpu().numpy().reshape(inp["dir"].shape)
     dev_loss = loss.item()
     assert dev_loss == tb["rpn_loss"] or (np.isnan(dev_loss) and np.isnan(tb["rpn_loss"]))
     return got, head
@@ -101,6 +110,48 @@ def test_fixture_scenes(gold, gpu, name):
     assert not why, f"against the restatement\n{why}"
     # the one visible difference to the reference: the labels in forward_ret_dict are left as they were
     assert np.array_equal(head.forward_ret_dict["box_cls_labels"].cpu().numpy(), labels_before)
+
+
+@pytest.mark.parametrize("name", list(seq.edge_scene_cfgs()))
+def test_fixture_edge_scenes(edges, gpu, name):
+    """the second recorded set: bin edges, saturating and non-finite values, the head's real layout (three anchor tensors
+    through get_loss's own flattening), al_finish past 256 and 2048 partials"""
+    cfg = dict(seq.scenes(edges))[name]
+    assert cfg == CASES[name]
+    inp, want, ex = restated(("case", name), cfg)
+    rec = seq.recorded(edges, name)
+    got, head = through_get_loss(cfg, inp, gpu)
+    why, _ = seq.bound_report(got, ex, "the device")
+    assert not why, f"against exact()\n{why}"
+    why, _ = seq.bound_report(rec, seq.only(ex, rec), "the reference")
+    assert not why, why
+    assert not seq.zero_report(seq.only(got, rec), rec)
+    for k, v in rec.items():
+        assert np.array_equal(np.isnan(got[k]), np.isnan(v)), k          # NaNs at the reference's places
+    why = seq.report(got, want)
+    assert not why, f"against the restatement\n{why}"
+    if cfg.get("layout"):
+        assert len(head.anchors) == 3 and np.array_equal(head._modest_anchor_loss_anchors.cpu().numpy(), inp["anchors"])
+
+
+def test_no_anchors(gpu):
+    """N = 0: the four scalars are 0 and nothing else is written, with and without gradients"""
+    for bins in (2, 0):
+        for want_grad in (True, False):
+            z = lambda *shape: torch.zeros(shape, device=gpu)      # noqa: E731
+            out = torch.full((4,), SENTINEL, dtype=torch.int32, device=gpu).view(torch.float32)
+            ws = torch.full((max(ops.anchor_loss_workspace_bytes(2, 0), 256),), 0x5A, dtype=torch.uint8, device=gpu)
+            before = ws.clone()
+            grads_in = [z(2, 0, 3), z(2, 0, 7), z(2, 0, bins) if bins else None] if want_grad else [None, None, None]
+            losses, grads = ops.anchor_loss(z(2, 0, 3), z(2, 0, 7), z(2, 0, bins) if bins else None,
+                                            torch.zeros((2, 0), dtype=torch.int32, device=gpu), z(2, 0, 7), z(0, 7), torch.ones(7, device=gpu),
+                                            want_grad=want_grad, workspace=ws, out=[out] + grads_in)
+            assert losses.cpu().numpy().view(np.uint32).tolist() == [0, 0, 0, 0]
+            assert (grads is None) == (not want_grad)
+            if want_grad:
+                assert [g.shape for g in grads if g is not None] == [(2, 0, 3), (2, 0, 7)] + ([(2, 0, bins)] if bins else [])
+            # past the two counters the workspace is as it was
+            assert torch.equal(ws[256:], before[256:])
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

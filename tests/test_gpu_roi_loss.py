@@ -18,6 +18,7 @@ from modest_amd.utils import roi_head_loss as rhl
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roi_loss.npz")
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roi_loss_edges.npz")
 F = np.float32
 SENTINEL = 0x5A5A5A5A
 _restated = {}
@@ -106,6 +107,30 @@ def test_fixture_scenes(gold, gpu, name):
     # the one visible difference to the reference: the sizes in forward_ret_dict['gt_of_rois'] are left as they were
     after = head.forward_ret_dict["gt_of_rois"].cpu().numpy().reshape(gt_before.shape)
     assert np.array_equal(after.view(np.uint32), gt_before.view(np.uint32))
+
+
+@pytest.fixture(scope="module")
+def edges():
+    return dict(np.load(EDGES))
+
+
+@pytest.mark.parametrize("name", list(seq.edge_scene_cfgs()))
+def test_fixture_edge_scenes(edges, gpu, name):
+    """the second recorded set: non-finite and huge values on foreground rows, with and without the corner term"""
+    cfg = dict(seq.scenes(edges))[name]
+    assert cfg == CASES[name]
+    inp, want, ex = restated(("case", name), cfg)
+    rec = seq.recorded(edges, name)
+    got, head = through_get_loss(cfg, inp, gpu)
+    why, _ = seq.bound_report(got, ex, "the device")
+    assert not why, f"against exact()\n{why}"
+    why, _ = seq.bound_report(rec, ex, "the reference")
+    assert not why, why
+    assert not seq.zero_report(got, rec)
+    for k, v in rec.items():
+        assert np.array_equal(np.isnan(got[k]), np.isnan(v)), k          # NaNs at the reference's places
+    why = seq.report(got, want)
+    assert not why, f"against the restatement\n{why}"
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

@@ -15,11 +15,12 @@ import pytest
 
 import anchor_loss_seq
 import point_loss_seq as seq
-from point_loss_cases import CASES
+from point_loss_cases import CASES, MAY_HOLD_NAN
 
 F = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "point_loss.npz")
+EDGES = os.path.join(HERE, "golden", "point_loss_edges.npz")
 SCENES = ["pointrcnn", "pointrcnn3", "parta2", "parta2_nobox", "pvrcnn", "nopos", "edge"]
 
 
@@ -187,7 +188,8 @@ def test_edge_cases_through_the_restatement(name):
     R = cfg["B"] * cfg["N"]
     assert sorted(ours) == sorted(["table", "grad_cls"] + [f"grad_{t}" for t in terms[1:]])
     assert ours["table"][4] == pos.sum() and (ours["grad_cls"][~cared] == 0).all()
-    assert not any(np.isnan(v).any() for v in ours.values())
+    for k, v in ours.items():      # a NaN only in the named outputs of the named cases
+        assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
     assert ours["grad_cls"].shape == (R, cfg["num_class"])
     for k, cols in (("grad_part", 3), ("grad_box", cfg["code"])):
         if k in ours:
@@ -195,6 +197,80 @@ def test_edge_cases_through_the_restatement(name):
             assert (ours[k][pos] != 0).any() == bool(pos.any())
     if not pos.any():
         assert ours["table"][1] == 0 and ours["table"][2] == 0 and ours["table"][3] == ours["table"][0]
+
+
+# ------------------------------------------------------------------------------------------------ the recorded edge scenes
+@pytest.fixture(scope="module")
+def edges():
+    return dict(np.load(EDGES))
+
+
+def scene_mismatch(cfg, inp, ours, dec, rec):
+    """the comparison of a recorded scene -> text, "" when everything agrees: the recorded values and ours within the bound of
+    exact() along ours' decisions with NaNs at the same places, and the zero patterns"""
+    ex = seq.exact(inp, cfg, dec)
+    return "\n".join(line for line in (seq.bound_report(ours, ex, "ours")[0], seq.bound_report(rec, ex, "the reference")[0],
+                                       seq.zero_report(ours, rec)) if line)
+
+
+def test_edges_fixture_is_small_and_holds_the_case_configs(edges):
+    assert os.path.getsize(EDGES) <= 64 * 1024
+    cfgs = seq.edge_scene_cfgs()
+    assert [n for n, _ in seq.scenes(edges)] == list(cfgs)
+    for name, cfg in seq.scenes(edges):
+        assert cfg == json.loads(json.dumps(cfgs[name])) == json.loads(json.dumps(CASES[name])), name
+        assert set(seq.recorded(edges, name)) == set(case(name)[2]), name
+    assert cfgs["nonfinite_l1"]["beta"] == 0.0 and {seq.terms_of(c) for c in cfgs.values()} == {("cls", "box"), ("cls", "part", "box")}
+
+
+def test_edge_scenes_lie_within_the_derived_bound(edges):
+    worst = {}
+    for name, cfg in seq.scenes(edges):
+        cfg, inp, ours, dec = case(name)
+        rec, ex = seq.recorded(edges, name), seq.exact(inp, cfg, dec)
+        why = scene_mismatch(cfg, inp, ours, dec, rec)
+        assert not why, f"{name}\n{why}"
+        for who, got in (("ours", ours), ("reference", rec)):
+            for k, v in seq.bound_report(got, ex, who)[1].items():
+                worst[(who, k)] = max(worst.get((who, k), 0.0), v)
+        for k, v in rec.items():
+            assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
+        # the special part and box values sit on positive rows
+        pos = inp["labels"] > 0
+        for k in ("part", "part_t", "box", "box_t"):
+            if k in inp:
+                assert np.isfinite(inp[k][~pos]).all() and (np.abs(inp[k][~pos]) < 20).all(), (name, k)
+    print({f"{w} {k}": round(v, 3) for (w, k), v in sorted(worst.items())})
+    assert all(v <= 1.0 for v in worst.values())
+    cfg, inp, ours, dec = case("nonfinite_inf")
+    assert np.isposinf(ours["table"][[2, 3]]).all() and np.isposinf(seq.recorded(edges, "nonfinite_inf")["table"][[2, 3]]).all()
+
+
+def test_the_smooth_l1_gradient_without_the_dead_share_fails_the_recorded_scene(edges):
+    rows = seq.SPECIAL_ROWS
+    cfg, inp, ours, dec = case("nonfinite")
+    rec = seq.recorded(edges, "nonfinite")
+    assert not scene_mismatch(cfg, inp, ours, dec, rec)
+    bad, bad_dec = seq._evaluate(inp, cfg, None, (seq.NO_DEAD_SHARE,))
+    why = scene_mismatch(cfg, inp, bad, bad_dec, rec)
+    assert "grad_box" in why and seq.report(bad, ours)
+    # the elements the share turns from finite to NaN: a NaN or infinite box value, an infinite box label
+    assert np.argwhere(np.isnan(ours["grad_box"]) & ~np.isnan(bad["grad_box"])).tolist() == [[rows[26 + j], 1] for j in range(4)]
+    assert np.array_equal(np.isnan(ours["grad_box"]), np.isnan(rec["grad_box"]))
+    cfg, inp, ours, dec = case("nonfinite_l1")          # WeightedL1Loss has no where(): nothing changes
+    assert same_bits(seq.restate(inp, cfg, (seq.NO_DEAD_SHARE,)), ours)
+
+
+def test_what_is_not_recorded_is_pinned():
+    """outside the contract: a NaN part logit, where the reference raises, and -88.9 against a part
+    label above 0, where a float32 sigmoid is exactly 0"""
+    cfg, inp, ours, dec = case("nan_part")
+    at = np.isnan(inp["part"])
+    assert at.sum() == 1 and np.array_equal(np.isnan(ours["grad_part"]), at) and np.isnan(ours["table"][[1, 3]]).all()
+    assert not np.isnan(ours["table"][[0, 2]]).any()
+    cfg, inp, ours, dec = case("extreme_sigmoid")
+    at = (inp["part"] == F(-88.9)) & (inp["part_t"] > 0)
+    assert at.sum() == 2 and (ours["grad_part"][at] < 0).all() and (np.abs(ours["grad_part"][at]) < 1e-25).all()
 
 
 def test_cases_cover_what_they_name():

@@ -13,10 +13,11 @@ import pytest
 
 import anchor_loss_seq
 import roi_loss_seq as seq
-from roi_loss_cases import CASES
+from roi_loss_cases import CASES, MAY_HOLD_NAN
 
 F = np.float32
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roi_loss.npz")
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roi_loss_edges.npz")
 SCENES = ["pointrcnn", "pvrcnn", "nofg", "nocorner", "wide", "edge"]
 
 
@@ -159,12 +160,13 @@ def test_edge_cases_through_the_restatement(name):
     fg, valid = inp["mask"] > 0, inp["labels"] >= 0
     assert (ours["grad_reg"][~fg] == 0).all() and (ours["grad_cls"][~valid] == 0).all()
     assert ours["table"][4] == fg.sum() and ours["table"][5] == valid.sum()
-    assert not any(np.isnan(v).any() for v in ours.values())
+    for k, v in ours.items():      # a NaN only in the named outputs of the named cases
+        assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
     assert ours["grad_reg"].shape == (cfg["B"] * cfg["M"], cfg["code"]) and inp["gt"].shape[1] == cfg["gt_cols"]
-    if fg.any():
-        assert (ours["grad_reg"][fg] != 0).any() and ours["table"][1] > 0 and (ours["table"][2] > 0) == bool(cfg["corner"])
-    else:
+    if not fg.any():
         assert ours["table"][1] == 0 and ours["table"][2] == 0 and ours["table"][3] == ours["table"][0]
+    elif name not in MAY_HOLD_NAN:
+        assert (ours["grad_reg"][fg] != 0).any() and ours["table"][1] > 0 and (ours["table"][2] > 0) == bool(cfg["corner"])
 
 
 def test_cases_cover_what_they_name():
@@ -194,6 +196,85 @@ def test_cases_cover_what_they_name():
     other = dict(inp, gt=inp["gt"].copy(), src=inp["src"].copy())
     other["gt"][:, 7:], other["src"][:, 7:] = F(np.nan), F(np.inf)
     assert not seq.report(seq.restate(other, cfg), ours)
+
+
+# ------------------------------------------------------------------------------------------------ the recorded edge scenes
+@pytest.fixture(scope="module")
+def edges():
+    return dict(np.load(EDGES))
+
+
+def scene_mismatch(cfg, inp, ours, dec, rec):
+    """the comparison of a recorded scene -> text, "" when everything agrees: the recorded values and ours within the bound of
+    exact() along ours' decisions with NaNs at the same places, and the zero patterns"""
+    ex = seq.exact(inp, cfg, dec)
+    return "\n".join(line for line in (seq.bound_report(ours, ex, "ours")[0], seq.bound_report(rec, ex, "the reference")[0],
+                                       seq.zero_report(ours, rec)) if line)
+
+
+def test_edges_fixture_is_small_and_holds_the_case_configs(edges):
+    assert os.path.getsize(EDGES) <= 64 * 1024
+    cfgs = seq.edge_scene_cfgs()
+    assert [n for n, _ in seq.scenes(edges)] == list(cfgs)
+    for name, cfg in seq.scenes(edges):
+        assert cfg == json.loads(json.dumps(cfgs[name])) == json.loads(json.dumps(CASES[name])), name
+    assert cfgs["nonfinite_corner"]["corner"] and cfgs["extreme_corner"]["corner"] and cfgs["nonfinite_l1"]["beta"] == 0.0
+
+
+def test_edge_scenes_lie_within_the_derived_bound(edges):
+    worst = {}
+    for name, cfg in seq.scenes(edges):
+        cfg, inp, ours, dec = case(name)
+        rec, ex = seq.recorded(edges, name), seq.exact(inp, cfg, dec)
+        why = scene_mismatch(cfg, inp, ours, dec, rec)
+        assert not why, f"{name}\n{why}"
+        for who, got in (("ours", ours), ("reference", rec)):
+            for k, v in seq.bound_report(got, ex, who)[1].items():
+                worst[(who, k)] = max(worst.get((who, k), 0.0), v)
+        for k, v in rec.items():
+            assert np.isnan(v).any() == (k in MAY_HOLD_NAN.get(name, ())), (name, k)
+        # the special values sit on foreground rows (the logits on rows that are valid and not foreground)
+        fg = inp["mask"] > 0
+        assert np.isfinite(inp["reg"][~fg]).all() and np.isfinite(inp["gt"][~fg]).all() and (np.abs(inp["reg"][~fg]) < 10).all()
+        assert not np.isfinite(inp["reg"][fg]).all() or (np.abs(inp["reg"][fg]) >= 1e20).any()
+    print({f"{w} {k}": round(v, 3) for (w, k), v in sorted(worst.items())})
+    assert all(v <= 1.0 for v in worst.values())
+    cfg, inp, ours, dec = case("nonfinite_inf")
+    assert np.isposinf(ours["table"][[1, 3]]).all() and np.isposinf(seq.recorded(edges, "nonfinite_inf")["table"][[1, 3]]).all()
+    cfg, inp, ours, dec = case("extreme_corner")      # squared corner distances past float32: an infinite corner term
+    assert np.isposinf(ours["table"][2]) and np.isposinf(seq.recorded(edges, "extreme_corner")["table"][2])
+    assert any(dec[f"na_inf{k}"].any() for k in range(8))
+
+
+def test_the_smooth_l1_gradient_without_the_dead_share_fails_the_recorded_scenes(edges):
+    rows = np.arange(0, 120, 3)
+    for name, turned in (("nonfinite", [[rows[10], 1], [rows[11], 1], [rows[12], 1], [rows[13], 6], [rows[14], 6], [rows[15], 6], [rows[16], 1],
+                                       [rows[17], 6]]),
+                         ("nonfinite_corner", [[rows[11], 2], [rows[11], 5], [rows[12], 2], [rows[12], 5], [rows[16], 1], [rows[17], 6]])):
+        cfg, inp, ours, dec = case(name)
+        rec = seq.recorded(edges, name)
+        assert not scene_mismatch(cfg, inp, ours, dec, rec)
+        bad, bad_dec = seq._evaluate(inp, cfg, None, (seq.NO_DEAD_SHARE,))
+        why = scene_mismatch(cfg, inp, bad, bad_dec, rec)
+        assert "grad_reg" in why and seq.report(bad, ours), name
+        # the elements the share turns from finite to NaN (with the corner term: its z and dz paths, whose unit vector is
+        # z / inf = 0, on top of the smooth L1's own)
+        assert np.argwhere(np.isnan(ours["grad_reg"]) & ~np.isnan(bad["grad_reg"])).tolist() == turned, name
+        assert np.array_equal(np.isnan(ours["grad_reg"]), np.isnan(rec["grad_reg"]))
+    cfg, inp, ours, dec = case("nonfinite_l1")          # WeightedL1Loss has no where(): nothing changes
+    assert not seq.report(seq.restate(inp, cfg, (seq.NO_DEAD_SHARE,)), ours)
+
+
+def test_what_is_not_recorded_is_pinned():
+    """outside the contract: a NaN logit, where the reference raises, and -88.9 against a label of 1,
+    where a float32 sigmoid is exactly 0"""
+    cfg, inp, ours, dec = case("nan_cls")
+    at = np.isnan(inp["cls"])
+    assert at.sum() == 2 and np.array_equal(np.isnan(ours["grad_cls"]), at) and np.isnan(ours["table"][[0, 3]]).all()
+    assert not np.isnan(ours["table"][[1, 2]]).any() and not np.isnan(ours["grad_reg"]).any()
+    cfg, inp, ours, dec = case("extreme_sigmoid")
+    at = (inp["cls"] == F(-88.9)) & (inp["labels"] > 0)
+    assert at.sum() == 1 and (ours["grad_cls"][at] < 0).all() and (np.abs(ours["grad_cls"][at]) < 1e-25).all()
 
 
 # which case each mis-statement of the contract must change, and in which output

@@ -11,7 +11,12 @@ specials by tests/anchor_loss_seq.py:make_inputs), the four scalars and the thre
 tool asserts that the restatement and the recorded values lie within the derived bound of ``exact()`` in every element, that
 the zero patterns of the gradients agree, and prints the largest error-to-bound ratio per output.
 
+A second config set (``anchor_loss_seq.edge_scene_cfgs``: headings at every direction-bin edge and its float32 neighbours,
+saturating and non-finite direction logits, non-finite and huge box values and class logits, the head's real layout of
+three anchor tensors) goes into tests/golden/anchor_loss_edges.npz, under the same assertions.
+
 Usage:  python tools/make_golden_anchor_loss.py        (writes tests/golden/anchor_loss.npz)
+        python tools/make_golden_anchor_loss.py edges  (writes tests/golden/anchor_loss_edges.npz)
 """
 import json
 import os
@@ -34,6 +39,7 @@ import numpy as np
 import torch
 ref, root, job = sys.argv[1], sys.argv[2], pickle.load(open(sys.argv[3], "rb"))
 sys.path.insert(0, root)
+sys.path.insert(0, os.path.join(root, "tests"))
 for name in ("pcdet", "pcdet.models", "pcdet.models.dense_heads", "pcdet.models.dense_heads.target_assigner", "pcdet.utils",
              "pcdet.ops", "pcdet.ops.iou3d_nms", "pcdet.ops.roiaware_pool3d"):
     m = types.ModuleType(name)
@@ -56,13 +62,21 @@ for name, (cfg, inp) in job.items():
                          DIR_OFFSET=cfg["dir_offset"], NUM_DIR_BINS=cfg["bins"], USE_MULTIHEAD=False)
     head.num_class, head.num_anchors_per_location, head.use_multihead = cfg["num_class"], 1, False
     head.anchors = [torch.from_numpy(inp["anchors"].copy()).view(1, 1, -1, 1, 1, inp["anchors"].shape[-1])]
+    shape = lambda k: inp[k].shape
+    if cfg.get("layout"):      # the head's real layout: three anchor tensors, six anchors per location, (B, H, W, 6 * columns)
+        import anchor_loss_seq
+        H, W = cfg["layout"]
+        head.num_anchors_per_location = 6
+        head.anchors = [torch.from_numpy(t) for t in anchor_loss_seq.anchor_tensors(cfg, inp["anchors"])]
+        shape = lambda k: (inp[k].shape[0], H, W, 6 * inp[k].shape[2])
     head.cls_loss_func = loss_utils.SigmoidFocalClassificationLoss(alpha=0.25, gamma=2.0)
     if cfg["beta"] == 0:
         head.reg_loss_func = loss_utils.WeightedL1Loss(code_weights=cfg["code_weights"])
     else:
         head.reg_loss_func = loss_utils.WeightedSmoothL1Loss(beta=cfg["beta"], code_weights=cfg["code_weights"])
     head.dir_loss_func = loss_utils.WeightedCrossEntropyLoss()
-    preds = {k: torch.from_numpy(inp[k].copy()).requires_grad_(True) for k in ("cls", "box", "dir") if inp[k] is not None}
+    preds = {k: torch.from_numpy(inp[k].copy().reshape(shape(k))).requires_grad_(True) for k in ("cls", "box", "dir")
+             if inp[k] is not None}
     head.forward_ret_dict = dict(cls_preds=preds["cls"], box_preds=preds["box"],
                                  box_cls_labels=torch.from_numpy(inp["labels"].copy()),
                                  box_reg_targets=torch.from_numpy(inp["tg"].copy()))
@@ -71,10 +85,10 @@ for name, (cfg, inp) in job.items():
     loss, tb = head.get_loss()
     loss.backward()
     out = dict(losses=np.array([tb["rpn_loss_cls"], tb["rpn_loss_loc"], tb.get("rpn_loss_dir", 0.0), tb["rpn_loss"]], dtype=np.float32),
-               grad_cls=preds["cls"].grad.numpy(), grad_box=preds["box"].grad.numpy())
+               grad_cls=preds["cls"].grad.numpy().reshape(inp["cls"].shape), grad_box=preds["box"].grad.numpy().reshape(inp["box"].shape))
     assert np.float32(loss.item()) == out["losses"][3] or np.isnan(out["losses"][3])
     if "dir" in preds:
-        out["grad_dir"] = preds["dir"].grad.numpy()
+        out["grad_dir"] = preds["dir"].grad.numpy().reshape(inp["dir"].shape)
     res[name] = out
 pickle.dump(res, open(sys.argv[4], "wb"))
 """
@@ -105,9 +119,10 @@ def run_reference(job):
         return pickle.load(open(dst, "rb"))
 
 
-def main():
+def main(which="scenes"):
     import anchor_loss_seq as seq
-    cfgs = configs(seq)
+    assert which in ("scenes", "edges"), which
+    cfgs = configs(seq) if which == "scenes" else seq.edge_scene_cfgs()
     job = {n: (cfg, seq.make_inputs(cfg)) for n, cfg in cfgs.items()}
     ref = run_reference(job)
     store = {"scenes": np.array(json.dumps(list(cfgs)))}
@@ -124,9 +139,11 @@ def main():
         assert set(ours) == set(ref[name])
         store[f"{name}/cfg"] = np.array(json.dumps(cfg))
         for k, v in ref[name].items():
-            store[f"{name}/{k}"] = v
-    assert np.isnan(ref["nan6"]["losses"][[1, 3]]).all() and not np.isnan(ref["edge"]["losses"]).any()
-    path = os.path.join(GOLD, "anchor_loss.npz")
+            if k in cfg.get("record", seq.OUTPUTS):      # a direction scene keeps the scalars and grad_dir alone
+                store[f"{name}/{k}"] = v
+    if which == "scenes":
+        assert np.isnan(ref["nan6"]["losses"][[1, 3]]).all() and not np.isnan(ref["edge"]["losses"]).any()
+    path = os.path.join(GOLD, "anchor_loss.npz" if which == "scenes" else "anchor_loss_edges.npz")
     np.savez_compressed(path, **store)
     for (who, k), v in sorted(worst.items()):
         print(f"largest error / bound, {who:9s} {k:9s} {v:.3f}")
@@ -134,4 +151,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])

@@ -17,7 +17,11 @@ restatement and the recorded values lie within the derived bound of ``exact()`` 
 that the zero patterns of the gradients agree, that point_pos_num agrees and that tb_dict holds the head's keys in the
 reference's order, and prints the largest error-to-bound ratio per output.
 
+A second config set (``point_loss_seq.edge_scene_cfgs``: NaN and infinite box values and labels, infinite focal and part
+logits, huge finite values, all on positive rows) goes into tests/golden/point_loss_edges.npz, under the same assertions.
+
 Usage:  python tools/make_golden_point_loss.py        (writes tests/golden/point_loss.npz)
+        python tools/make_golden_point_loss.py edges  (writes tests/golden/point_loss_edges.npz)
 """
 import json
 import os
@@ -116,9 +120,10 @@ def run_reference(job):
         return pickle.load(open(dst, "rb"))
 
 
-def main():
+def main(which="scenes"):
     import point_loss_seq as seq
-    cfgs = configs(seq)
+    assert which in ("scenes", "edges"), which
+    cfgs = configs(seq) if which == "scenes" else seq.edge_scene_cfgs()
     job = {n: (cfg, seq.make_inputs(cfg), seq.terms_of(cfg)) for n, cfg in cfgs.items()}
     ref = run_reference(job)
     store = {"scenes": np.array(json.dumps(list(cfgs)))}
@@ -143,8 +148,9 @@ def main():
         store[f"{name}/cfg"] = np.array(json.dumps(cfg))
         for k, v in rec.items():
             store[f"{name}/{k}"] = v
-    assert not np.isnan(ref["edge"]["table"]).any() and ref["nopos"]["table"][4] == 0
-    path = os.path.join(GOLD, "point_loss.npz")
+    if which == "scenes":
+        assert not np.isnan(ref["edge"]["table"]).any() and ref["nopos"]["table"][4] == 0
+    path = os.path.join(GOLD, "point_loss.npz" if which == "scenes" else "point_loss_edges.npz")
     np.savez_compressed(path, **store)
     for (who, k), v in sorted(worst.items()):
         print(f"largest error / bound, {who:9s} {k:9s} {v:.3f}")
@@ -152,4 +158,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])

@@ -19,7 +19,12 @@ same places, that the zero patterns of the gradients agree, that fg_sum agrees a
 gt_of_rois clamped in place (the visible difference), and prints the largest error-to-bound ratio per output (DESIGN.md
 section 7q).
 
+A second config set (``roi_loss_seq.edge_scene_cfgs``: NaN and infinite values in rcnn_reg and in a gt on foreground rows,
+infinite logits, huge finite values, each with and without the corner term) goes into tests/golden/roi_loss_edges.npz, under
+the same assertions.
+
 Usage:  python tools/make_golden_roi_loss.py        (writes tests/golden/roi_loss.npz)
+        python tools/make_golden_roi_loss.py edges  (writes tests/golden/roi_loss_edges.npz)
 """
 import json
 import os
@@ -117,9 +122,10 @@ def run_reference(job):
         return pickle.load(open(dst, "rb"))
 
 
-def main():
+def main(which="scenes"):
     import roi_loss_seq as seq
-    cfgs = configs(seq)
+    assert which in ("scenes", "edges"), which
+    cfgs = configs(seq) if which == "scenes" else seq.edge_scene_cfgs()
     job = {n: (cfg, seq.make_inputs(cfg)) for n, cfg in cfgs.items()}
     ref = run_reference(job)
     store = {"scenes": np.array(json.dumps(list(cfgs)))}
@@ -143,8 +149,9 @@ def main():
         store[f"{name}/cfg"] = np.array(json.dumps(cfg))
         for k, v in rec.items():
             store[f"{name}/{k}"] = v
-    assert not np.isnan(ref["edge"]["table"]).any() and ref["nofg"]["table"][4] == 0
-    path = os.path.join(GOLD, "roi_loss.npz")
+    if which == "scenes":
+        assert not np.isnan(ref["edge"]["table"]).any() and ref["nofg"]["table"][4] == 0
+    path = os.path.join(GOLD, "roi_loss.npz" if which == "scenes" else "roi_loss_edges.npz")
     np.savez_compressed(path, **store)
     for (who, k), v in sorted(worst.items()):
         print(f"largest error / bound, {who:9s} {k:9s} {v:.3f}")
@@ -152,4 +159,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])
