@@ -22,11 +22,11 @@
 #include "modest_hip.h"
 #include "prop_walk.h"
 #include "iou3d_steps.h"
+#include "loss_terms.h"
 
 namespace {
 
-// torch.sigmoid's value by the project's rule for log / cos / sin: the double function, rounded once
-__device__ __forceinline__ float sigmoid_f32(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
+using modest::loss::sigmoid_f32;   // torch.sigmoid's value by the project's rule for log / cos / sin: the double function, rounded once
 
 // prop_keys on the NORMALISED score, with the score threshold: a row that fails  score >= thresh  (a NaN fails) is in no sample
 __global__ __launch_bounds__(256) void post_keys(int64_t n, int b, int64_t rows_per_sample, const float *__restrict__ cls,

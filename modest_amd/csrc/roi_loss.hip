@@ -8,45 +8,36 @@
 //   rl_loss    one lane per RoI, 256 per workgroup.  Every workgroup first counts the foreground rows (reg_valid_mask > 0) and
 //              the valid class rows (label >= 0) of the WHOLE arrays with ballot + popcount into LDS integers (the arrays are R
 //              words and live in L2; no count kernel, no atomic), then the lane computes its row's three terms and writes its
-//              gradient rows; the three sums of the workgroup go through the fixed tree of section 7p (xor butterfly over the
-//              wavefront, (w0 + w1) + (w2 + w3) in LDS) into the partials array;
-//   rl_finish  one workgroup: lane t adds partials t, t + 256, ... in ascending order, then the same tree, then the table;
+//              gradient rows; the three sums of the workgroup into the partials array;
+//   rl_finish  one workgroup: the partials' sums, then the table;
 //   rl_scale   (modest_roi_loss_backward) the two gradient buffers times the upstream gradient read from the device.
-// No float atomics: no result depends on arrival order.  The arithmetic is the contract of DESIGN.md section 7q: float32, one
-// rounding per operation in the written order (built with -ffp-contract=off), exp / log / log1p / sin / cos and the sigmoid as
-// the double function rounded once, sqrt and / correctly rounded; the gradient follows autograd's own chain through the
-// reference's expression, path by path.  The 8 corners and code columns 0 .. 6 are unrolled: no indexed per-thread array.
+// The arithmetic, the terms and the summation tree are those of csrc/loss_terms.h (DESIGN.md sections 7p and 7q); sin / cos are
+// csrc/trig_f32.h's, sqrt is correctly rounded.  The float label load, the encoding and the corner term are this file's own.
+// The 8 corners and code columns 0 .. 6 are unrolled: no indexed per-thread array.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "common.h"
 #include "modest_hip.h"
+#include "loss_terms.h"
 #include "trig_f32.h"
 
 namespace {
 
-constexpr int RL_T = 256;          // lanes (rows) per workgroup
-constexpr int RL_WAVES = RL_T / 64;
+using namespace modest::loss;
+
 constexpr int RL_MAX_CODE = 16;
 constexpr int64_t RL_MAX_ROWS = 1 << 20;   // every workgroup counts over all rows: R^2 / 256 reads
 
-__device__ __forceinline__ float exp_f32(float x) { return (float)exp((double)x); }
-__device__ __forceinline__ float log_f32(float x) { return (float)log((double)x); }
-__device__ __forceinline__ float log1p_f32(float x) { return (float)log1p((double)x); }
-__device__ __forceinline__ float sigmoid_f32(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
-// torch's sgn of a real: (0 < x) - (x < 0), so 0 for a NaN
-__device__ __forceinline__ float sign_f32(float x) { return (float)((0.f < x) - (x < 0.f)); }
-// torch's clamp(min=lo): a NaN stays a NaN
-__device__ __forceinline__ float at_least(float v, float lo) { return v < lo ? lo : v; }
-
 struct RoiLossParams {
     int64_t r, blocks;
-    int code, label_kind, mask64, corner, l1, want_grad;   // label_kind 0 int32, 1 int64, 2 float32
+    int code, label_kind, mask64, corner, want_grad;   // label_kind 0 int32, 1 int64, 2 float32
     int64_t gt_stride, src_stride;
     const float *cls, *reg, *gt, *src, *rois, *cw;
     const void *labels, *mask;
-    float beta, half_beta, w_cls, w_reg, w_corner, tiny, pi, floor100, eps12;
+    SmoothL1 sl1;
+    float w_cls, w_reg, w_corner, tiny, pi, floor100, eps12;
     float *gcls, *greg, *out;
     float *part;                   // (3, blocks) workgroup sums
 };
@@ -72,12 +63,6 @@ __device__ __forceinline__ float label_at(const RoiLossParams &p, int64_t row, b
     return (float)v;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
 // column k of ResidualCoder.encode_torch of the canonical gt against the roi with centre and heading zeroed
 __device__ __forceinline__ float encode_col(const RoiLossParams &p, int k, const float *g, const float *roi, float diag_c, float dz_c) {
     if (k < 2) return g[k] / diag_c;
@@ -87,31 +72,12 @@ __device__ __forceinline__ float encode_col(const RoiLossParams &p, int k, const
     return g[k] - roi[k];
 }
 
-// the smooth-L1 term of one column: -> its value, its gradient to the input through *grad
-__device__ __forceinline__ float sl1_col(const RoiLossParams &p, int k, float in, float tg, float gl, float *grad) {
-    const bool replaced = tg != tg;           // a NaN target is replaced by the input
-    if (replaced) tg = in;
-    const float cw = p.cw[k];
-    const float d = (in - tg) * cw;
-    const float nrm = fabsf(d);
-    const bool quad = !p.l1 && nrm < p.beta;
-    const float v = p.l1 ? nrm : (quad ? ((0.5f * (nrm * nrm)) / p.beta) : (nrm - p.half_beta));
-    // where() hands the branch not taken a zero and pow's backward multiplies it by 2 n: +0 for a finite n (gl + 0 is
-    // gl), a NaN for an infinite or NaN one, as autograd gives it
-    const float dead = ((0.f / p.beta) * 0.5f) * (2.f * nrm);
-    const float g_n = quad ? (((gl / p.beta) * 0.5f) * (2.f * nrm)) : (p.l1 ? gl : gl + dead);
-    const float g_d = (g_n * sign_f32(d)) * cw;
-    *grad = replaced ? g_d + (-g_d) : g_d;    // where(isnan): the target's share goes to the input and cancels
-    return v;
-}
-
-__global__ __launch_bounds__(RL_T) void rl_loss(RoiLossParams p) {
-    __shared__ int s_cnt[2][RL_WAVES];
-    __shared__ float s_sum[3][RL_WAVES];
+__global__ __launch_bounds__(LANES) void rl_loss(RoiLossParams p) {
+    __shared__ int s_cnt[2][WAVES];
     const int tid = threadIdx.x;
     // ---- the two counts over the whole arrays
     int n_fg = 0, n_valid = 0;
-    for (int64_t j0 = 0; j0 < p.r; j0 += RL_T) {
+    for (int64_t j0 = 0; j0 < p.r; j0 += LANES) {
         const int64_t j = j0 + tid;
         bool valid = false, fg = false;
         if (j < p.r) {
@@ -129,23 +95,15 @@ __global__ __launch_bounds__(RL_T) void rl_loss(RoiLossParams p) {
     const int fg_sum = (s_cnt[0][0] + s_cnt[0][1]) + (s_cnt[0][2] + s_cnt[0][3]);
     const int valid_sum = (s_cnt[1][0] + s_cnt[1][1]) + (s_cnt[1][2] + s_cnt[1][3]);
 
-    const int64_t row = (int64_t)blockIdx.x * RL_T + tid;
+    const int64_t row = (int64_t)blockIdx.x * LANES + tid;
     float sum_cls = 0.f, sum_reg = 0.f, sum_corner = 0.f;
     if (row < p.r) {
         // ---- classification: binary cross entropy of the sigmoid
         bool valid;
         const float t = label_at(p, row, valid);
         if (valid) {
-            const float x = p.cls[row];
-            const float s = sigmoid_f32(x);
-            const float la = at_least(log1p_f32(-s), p.floor100), lb = at_least(log_f32(s), p.floor100);
-            sum_cls = (t - 1.f) * la - t * lb;
-            if (p.want_grad) {
-                const float g0 = p.w_cls / fmaxf((float)valid_sum, 1.f);
-                const float oms = 1.f - s;
-                const float g_s = (g0 * (s - t)) / at_least(oms * s, p.eps12);
-                p.gcls[row] = (g_s * oms) * s;
-            }
+            const float g0 = p.w_cls / fmaxf((float)valid_sum, 1.f);
+            sum_cls = bce_term(p.cls[row], t, g0, p.floor100, p.eps12, p.want_grad ? p.gcls + row : nullptr);
         } else if (p.want_grad) {
             p.gcls[row] = 0.f;
         }
@@ -227,59 +185,35 @@ __global__ __launch_bounds__(RL_T) void rl_loss(RoiLossParams p) {
             const float gl = p.w_reg / fmaxf((float)fg_sum, 1.f);
 #pragma unroll
             for (int k = 0; k < 7; ++k) {
-                float gk;
-                sum_reg = sum_reg + sl1_col(p, k, in[k], encode_col(p, k, g, roi, diag_c, dz_c), gl, &gk);
+                float gk, g_t;
+                sum_reg = sum_reg + smooth_l1_term(in[k], encode_col(p, k, g, roi, diag_c, dz_c), p.cw[k], gl, p.sl1, gk, g_t);
                 if (gr) gr[k] = gk + gc[k];
             }
             for (int k = 7; k < p.code; ++k) {
-                float gk;
-                sum_reg = sum_reg + sl1_col(p, k, in[k], encode_col(p, k, g, roi, diag_c, dz_c), gl, &gk);
+                float gk, g_t;
+                sum_reg = sum_reg + smooth_l1_term(in[k], encode_col(p, k, g, roi, diag_c, dz_c), p.cw[k], gl, p.sl1, gk, g_t);
                 if (gr) gr[k] = gk;
             }
         } else if (gr) {
             for (int k = 0; k < p.code; ++k) gr[k] = 0.f;
         }
     }
-    const float a = wave_sum(sum_cls), l = wave_sum(sum_reg), c = wave_sum(sum_corner);
-    if ((tid & 63) == 0) {
-        s_sum[0][tid >> 6] = a;
-        s_sum[1][tid >> 6] = l;
-        s_sum[2][tid >> 6] = c;
-    }
-    __syncthreads();
-    if (tid < 3) p.part[tid * p.blocks + blockIdx.x] = (s_sum[tid][0] + s_sum[tid][1]) + (s_sum[tid][2] + s_sum[tid][3]);
+    workgroup_sums(sum_cls, sum_reg, sum_corner, p.part, p.blocks, blockIdx.x);
     if (blockIdx.x == 0 && tid == 0) {
         p.out[4] = (float)fg_sum;
         p.out[5] = (float)valid_sum;
     }
 }
 
-__global__ __launch_bounds__(RL_T) void rl_finish(RoiLossParams p) {
-    __shared__ float s_sum[3][RL_WAVES];
-    const int tid = threadIdx.x;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    // partials t, t + 256, ... in ascending order; an accumulator that starts at +0 is never -0
-    for (int64_t j = tid; j < p.blocks; j += RL_T) {
-        a0 = a0 + p.part[j];
-        a1 = a1 + p.part[p.blocks + j];
-        a2 = a2 + p.part[2 * p.blocks + j];
-    }
-    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-    if ((tid & 63) == 0) {
-        s_sum[0][tid >> 6] = a0;
-        s_sum[1][tid >> 6] = a1;
-        s_sum[2][tid >> 6] = a2;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const float v0 = (s_sum[0][0] + s_sum[0][1]) + (s_sum[0][2] + s_sum[0][3]);
-        const float v1 = (s_sum[1][0] + s_sum[1][1]) + (s_sum[1][2] + s_sum[1][3]);
-        const float v2 = (s_sum[2][0] + s_sum[2][1]) + (s_sum[2][2] + s_sum[2][3]);
+__global__ __launch_bounds__(LANES) void rl_finish(RoiLossParams p) {
+    float v[3];
+    finish_sums(p.part, p.blocks, v);
+    if (threadIdx.x == 0) {
         const float fg = p.blocks > 0 ? p.out[4] : 0.f, valid = p.blocks > 0 ? p.out[5] : 0.f;   // written by rl_loss, earlier on the stream
-        const float cls = (v0 / fmaxf(valid, 1.f)) * p.w_cls;
-        const float reg = (v1 / fmaxf(fg, 1.f)) * p.w_reg;
+        const float cls = (v[0] / fmaxf(valid, 1.f)) * p.w_cls;
+        const float reg = (v[1] / fmaxf(fg, 1.f)) * p.w_reg;
         const bool with_corner = p.corner && fg > 0.f;
-        const float corner = with_corner ? (v2 / fg) * p.w_corner : 0.f;
+        const float corner = with_corner ? (v[2] / fg) * p.w_corner : 0.f;
         p.out[0] = cls;
         p.out[1] = reg;
         p.out[2] = corner;
@@ -289,15 +223,11 @@ __global__ __launch_bounds__(RL_T) void rl_finish(RoiLossParams p) {
     }
 }
 
-__global__ __launch_bounds__(RL_T) void rl_scale(int64_t n0, int64_t n1, float *__restrict__ g0, float *__restrict__ g1,
-                                                const float *__restrict__ upstream) {
-    const float u = upstream[0];
-    const int64_t i = (int64_t)blockIdx.x * RL_T + threadIdx.x;
-    if (i < n0) g0[i] = g0[i] * u;
-    else if (i < n0 + n1) g1[i - n0] = g1[i - n0] * u;
+__global__ __launch_bounds__(LANES) void rl_scale(int64_t n0, int64_t n1, float *__restrict__ g0, float *__restrict__ g1,
+                                                 const float *__restrict__ upstream) {
+    scale_grads(n0, n1, 0, g0, g1, nullptr, upstream);
 }
 
-int64_t blocks_of(int64_t n) { return (n + RL_T - 1) / RL_T; }
 size_t ws_total(int64_t r) { return arena_sz(4 * 3 * (size_t)(blocks_of(r) > 0 ? blocks_of(r) : 1)); }
 
 }  // namespace
@@ -332,22 +262,21 @@ extern "C" int modest_roi_loss(int64_t n_rows, int code, const float *rcnn_cls_d
     RoiLossParams p;
     p.r = n_rows; p.blocks = blocks_of(n_rows);
     p.code = code; p.label_kind = label_kind; p.mask64 = mask_int64 ? 1 : 0; p.corner = corner ? 1 : 0;
-    p.l1 = (double)beta < 1e-5 ? 1 : 0;
     p.want_grad = want ? 1 : 0;
     p.gt_stride = gt_row_stride; p.src_stride = src_row_stride;
     p.cls = rcnn_cls_dev; p.reg = rcnn_reg_dev; p.gt = gt_of_rois_dev; p.src = gt_of_rois_src_dev; p.rois = rois_dev;
     p.cw = code_weights_dev; p.labels = cls_labels_dev; p.mask = reg_valid_mask_dev;
-    p.beta = beta; p.half_beta = (float)(0.5 * (double)beta);
+    p.sl1 = smooth_l1_of(beta);
     p.w_cls = cls_weight; p.w_reg = reg_weight; p.w_corner = corner_weight;
     p.tiny = (float)1e-5; p.pi = (float)3.14159265358979323846; p.floor100 = -100.f; p.eps12 = (float)1e-12;
     p.gcls = grad_cls_dev; p.greg = grad_reg_dev; p.out = table_dev;
     p.part = static_cast<float *>(workspace_dev);
     hipStream_t s = as_stream(stream);
     if (p.blocks > 0) {
-        rl_loss<<<(unsigned)p.blocks, RL_T, 0, s>>>(p);
+        rl_loss<<<(unsigned)p.blocks, LANES, 0, s>>>(p);
         MODEST_HIP_CHECK(hipGetLastError());
     }
-    rl_finish<<<1, RL_T, 0, s>>>(p);
+    rl_finish<<<1, LANES, 0, s>>>(p);
     MODEST_HIP_CHECK(hipGetLastError());
     return MODEST_OK;
 }
@@ -360,7 +289,7 @@ extern "C" int modest_roi_loss_backward(int64_t n_cls, int64_t n_reg, float *gra
     const int64_t total = n_cls + n_reg;
     if (total == 0) return MODEST_OK;
     MODEST_REQUIRE(upstream_dev, "NULL upstream gradient");
-    rl_scale<<<(unsigned)blocks_of(total), RL_T, 0, as_stream(stream)>>>(n_cls, n_reg, grad_cls_dev, grad_reg_dev, upstream_dev);
+    rl_scale<<<(unsigned)blocks_of(total), LANES, 0, as_stream(stream)>>>(n_cls, n_reg, grad_cls_dev, grad_reg_dev, upstream_dev);
     MODEST_HIP_CHECK(hipGetLastError());
     return MODEST_OK;
 }

@@ -2034,6 +2034,56 @@ def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: i
     return boxes, scores, labs, counts, recall
 
 
+# --------------------------------------------------------------------------- what the three head losses share
+def _loss_workspace_bytes(fn_name: str, *args) -> int:
+    nb = int(getattr(load(), fn_name)(*(int(a) for a in args)))
+    if nb < 0:
+        check(nb, fn_name)
+    return nb
+
+
+def _loss_out(want, out, dev):
+    """`want`: (name, shape, needed) per buffer -> the float32 buffers on `dev`, None where none is needed: new ones, or those
+    of `out` once they are found to be just these"""
+    if out is None:
+        return [torch.empty(shape, dtype=torch.float32, device=dev) if need else None for _, shape, need in want]
+    if len(out) != len(want):
+        raise ValueError(f"out must be ({', '.join(name for name, _, _ in want)})")
+    for t, (name, shape, need) in zip(out, want):
+        if (t is not None) != need:
+            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
+        if t is not None:
+            _dev(t, torch.float32, f"out {name}")
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
+    return out
+
+
+def _loss_workspace(nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    return _dev(workspace, torch.uint8, "workspace")
+
+
+def _loss_backward(fn_name: str, names, grads, upstream: torch.Tensor):
+    """`fn_name` on PyTorch's current stream: the gradient buffers `grads` (`names`; None where a term is absent) times the
+    float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
+    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("upstream must be a float32 device tensor of one element")
+    if len(grads) != len(names):
+        raise ValueError(f"grads must be ({', '.join(names)})")
+    for g in grads:
+        if g is not None:
+            _dev(g, torch.float32, "a gradient buffer")
+            if g.device != upstream.device:
+                raise ValueError("the gradient buffers and upstream are on different devices")
+    with torch.cuda.device(upstream.device):
+        check(getattr(load(), fn_name)(*(int(g.numel()) if g is not None else 0 for g in grads),
+                                       *(g.data_ptr() if g is not None else None for g in grads),
+                                       upstream.data_ptr(), _stream()), fn_name)
+    return grads
+
+
 # --------------------------------------------------------------------------- anchor-head loss (DESIGN.md section 7p)
 ANCHOR_LOSS_MAX_CLASS = 32      # class columns of an anchor
 ANCHOR_LOSS_MAX_CODE = 16       # box code columns
@@ -2042,10 +2092,7 @@ ANCHOR_LOSS_MAX_BATCH = 65535   # samples per call: the grid's second dimension
 
 
 def anchor_loss_workspace_bytes(batch_size: int, n_anchors: int) -> int:
-    nb = int(load().modest_anchor_loss_workspace_bytes(int(batch_size), int(n_anchors)))
-    if nb < 0:
-        check(nb, "modest_anchor_loss_workspace_bytes")
-    return nb
+    return _loss_workspace_bytes("modest_anchor_loss_workspace_bytes", batch_size, n_anchors)
 
 
 def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Optional[torch.Tensor], labels: torch.Tensor,
@@ -2104,25 +2151,9 @@ def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Opt
             raise ValueError(f"{name} is on {t.device}, cls_preds on {dev}")
     cls, box = cls_preds.contiguous(), box_preds.contiguous()
     dirp = dir_preds.contiguous() if dir_preds is not None else None
-    want = (("losses", (4,)), ("grad_cls", (B, N, K)), ("grad_box", (B, N, code)), ("grad_dir", (B, N, bins)))
-    if out is None:
-        out = [torch.empty(shape, dtype=torch.float32, device=dev) if (i == 0 or (want_grad and (i < 3 or dirp is not None))) else None
-               for i, (_, shape) in enumerate(want)]
-    if len(out) != 4:
-        raise ValueError("out must be (losses, grad_cls, grad_box, grad_dir)")
-    for i, (t, (name, shape)) in enumerate(zip(out, want)):
-        need = i == 0 or (want_grad and (i < 3 or dirp is not None))
-        if (t is not None) != need:
-            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
-        if t is not None:
-            _dev(t, torch.float32, f"out {name}")
-            if tuple(t.shape) != shape or t.device != dev:
-                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
-    losses, gcls, gbox, gdir = out
-    nbytes = anchor_loss_workspace_bytes(B, N)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    losses, gcls, gbox, gdir = _loss_out((("losses", (4,), True), ("grad_cls", (B, N, K), want_grad), ("grad_box", (B, N, code), want_grad),
+                                          ("grad_dir", (B, N, bins), want_grad and dirp is not None)), out, dev)
+    workspace = _loss_workspace(anchor_loss_workspace_bytes(B, N), workspace, dev)
     ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
     with torch.cuda.device(dev):
         check(load().modest_anchor_loss(B, N, K, code, bins, ptr(cls), ptr(box), ptr(dirp), ptr(labels),
@@ -2136,20 +2167,7 @@ def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Opt
 def anchor_loss_backward(grads, upstream: torch.Tensor):
     """modest_anchor_loss_backward on PyTorch's current stream: the gradient buffers of `anchor_loss` (grad_dir may be None)
     times the float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
-    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
-        raise ValueError("upstream must be a float32 device tensor of one element")
-    live = [g for g in grads if g is not None]
-    for g in live:
-        _dev(g, torch.float32, "a gradient buffer")
-        if g.device != upstream.device:
-            raise ValueError("the gradient buffers and upstream are on different devices")
-    gcls, gbox, gdir = grads
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    num = lambda t: int(t.numel()) if t is not None else 0       # noqa: E731
-    with torch.cuda.device(upstream.device):
-        check(load().modest_anchor_loss_backward(num(gcls), num(gbox), num(gdir), ptr(gcls), ptr(gbox), ptr(gdir),
-                                                 upstream.data_ptr(), _stream()), "modest_anchor_loss_backward")
-    return grads
+    return _loss_backward("modest_anchor_loss_backward", ("grad_cls", "grad_box", "grad_dir"), grads, upstream)
 
 
 # --------------------------------------------------------------------------- RoI-head loss (DESIGN.md section 7q)
@@ -2161,10 +2179,7 @@ _ROI_LOSS_LABELS = {torch.int32: 0, torch.int64: 1, torch.float32: 2}
 
 
 def roi_loss_workspace_bytes(n_rows: int) -> int:
-    nb = int(load().modest_roi_loss_workspace_bytes(int(n_rows)))
-    if nb < 0:
-        check(nb, "modest_roi_loss_workspace_bytes")
-    return nb
+    return _loss_workspace_bytes("modest_roi_loss_workspace_bytes", n_rows)
 
 
 def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: torch.Tensor, reg_valid_mask: torch.Tensor,
@@ -2219,25 +2234,8 @@ def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: to
         if t.device != dev:
             raise ValueError(f"{name} is on {t.device}, rcnn_cls on {dev}")
     cls, reg = rcnn_cls.reshape(-1).contiguous(), rcnn_reg.contiguous()
-    want = (("table", (6,)), ("grad_cls", (R,)), ("grad_reg", (R, code)))
-    if out is None:
-        out = [torch.empty(shape, dtype=torch.float32, device=dev) if (i == 0 or want_grad) else None
-               for i, (_, shape) in enumerate(want)]
-    if len(out) != 3:
-        raise ValueError("out must be (table, grad_cls, grad_reg)")
-    for i, (t, (name, shape)) in enumerate(zip(out, want)):
-        need = i == 0 or want_grad
-        if (t is not None) != need:
-            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
-        if t is not None:
-            _dev(t, torch.float32, f"out {name}")
-            if tuple(t.shape) != shape or t.device != dev:
-                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
-    table, gcls, greg = out
-    nbytes = roi_loss_workspace_bytes(R)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    table, gcls, greg = _loss_out((("table", (6,), True), ("grad_cls", (R,), want_grad), ("grad_reg", (R, code), want_grad)), out, dev)
+    workspace = _loss_workspace(roi_loss_workspace_bytes(R), workspace, dev)
     ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
     stride = lambda t: int(t.stride(0)) if R > 1 else int(t.shape[1])      # noqa: E731
     with torch.cuda.device(dev):
@@ -2253,19 +2251,7 @@ def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: to
 def roi_loss_backward(grads, upstream: torch.Tensor):
     """modest_roi_loss_backward on PyTorch's current stream: the two gradient buffers of `roi_loss` times the float32 device
     scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
-    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
-        raise ValueError("upstream must be a float32 device tensor of one element")
-    if len(grads) != 2:
-        raise ValueError("grads must be (grad_cls, grad_reg)")
-    for g in grads:
-        _dev(g, torch.float32, "a gradient buffer")
-        if g.device != upstream.device:
-            raise ValueError("the gradient buffers and upstream are on different devices")
-    gcls, greg = grads
-    with torch.cuda.device(upstream.device):
-        check(load().modest_roi_loss_backward(int(gcls.numel()), int(greg.numel()), gcls.data_ptr(), greg.data_ptr(),
-                                              upstream.data_ptr(), _stream()), "modest_roi_loss_backward")
-    return grads
+    return _loss_backward("modest_roi_loss_backward", ("grad_cls", "grad_reg"), grads, upstream)
 
 
 # --------------------------------------------------------------------------- point-head loss (DESIGN.md section 7r)
@@ -2277,10 +2263,7 @@ POINT_LOSS_TABLE = ("point_loss_cls", "point_loss_part", "point_loss_box", "poin
 
 
 def point_loss_workspace_bytes(n_rows: int) -> int:
-    nb = int(load().modest_point_loss_workspace_bytes(int(n_rows)))
-    if nb < 0:
-        check(nb, "modest_point_loss_workspace_bytes")
-    return nb
+    return _loss_workspace_bytes("modest_point_loss_workspace_bytes", n_rows)
 
 
 def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Optional[torch.Tensor] = None,
@@ -2348,24 +2331,10 @@ def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Option
     cls, labels = rows(cls_preds, K), labels.reshape(-1).contiguous()
     part, part_t = rows(part_preds, POINT_LOSS_PART), rows(part_labels, POINT_LOSS_PART)
     box, box_t = rows(box_preds, max(code, 1)), rows(box_labels, max(code, 1))
-    want = (("table", (5,), True), ("grad_cls", (N, K), want_grad), ("grad_part", (N, POINT_LOSS_PART), want_grad and with_part),
-            ("grad_box", (N, code), want_grad and with_box))
-    if out is None:
-        out = [torch.empty(shape, dtype=torch.float32, device=dev) if need else None for _, shape, need in want]
-    if len(out) != 4:
-        raise ValueError("out must be (table, grad_cls, grad_part, grad_box)")
-    for t, (name, shape, need) in zip(out, want):
-        if (t is not None) != need:
-            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
-        if t is not None:
-            _dev(t, torch.float32, f"out {name}")
-            if tuple(t.shape) != shape or t.device != dev:
-                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
-    table, gcls, gpart, gbox = out
-    nbytes = point_loss_workspace_bytes(N)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    table, gcls, gpart, gbox = _loss_out((("table", (5,), True), ("grad_cls", (N, K), want_grad),
+                                          ("grad_part", (N, POINT_LOSS_PART), want_grad and with_part),
+                                          ("grad_box", (N, code), want_grad and with_box)), out, dev)
+    workspace = _loss_workspace(point_loss_workspace_bytes(N), workspace, dev)
     ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
     with torch.cuda.device(dev):
         check(load().modest_point_loss(N, K, code, ptr(cls), ptr(labels), int(labels.dtype == torch.int64), ptr(part), ptr(part_t),
@@ -2378,19 +2347,4 @@ def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Option
 def point_loss_backward(grads, upstream: torch.Tensor):
     """modest_point_loss_backward on PyTorch's current stream: the gradient buffers of `point_loss` (grad_part and grad_box
     may be None) times the float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
-    if not torch.is_tensor(upstream) or not upstream.is_cuda or upstream.dtype != torch.float32 or upstream.numel() != 1:
-        raise ValueError("upstream must be a float32 device tensor of one element")
-    if len(grads) != 3:
-        raise ValueError("grads must be (grad_cls, grad_part, grad_box)")
-    for g in grads:
-        if g is not None:
-            _dev(g, torch.float32, "a gradient buffer")
-            if g.device != upstream.device:
-                raise ValueError("the gradient buffers and upstream are on different devices")
-    gcls, gpart, gbox = grads
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    num = lambda t: int(t.numel()) if t is not None else 0       # noqa: E731
-    with torch.cuda.device(upstream.device):
-        check(load().modest_point_loss_backward(num(gcls), num(gpart), num(gbox), ptr(gcls), ptr(gpart), ptr(gbox),
-                                                upstream.data_ptr(), _stream()), "modest_point_loss_backward")
-    return grads
+    return _loss_backward("modest_point_loss_backward", ("grad_cls", "grad_part", "grad_box"), grads, upstream)

@@ -23,7 +23,8 @@ One visible difference: with ``num_class == 1`` the reference overwrites the pos
 ``AnchorHeadTemplate``.
 """
 import torch
-from torch.autograd.function import once_differentiable
+
+from ._head_loss import HeadLossFunction, _get, buffers, code_weights_tensor, read_table, replaced_get_loss
 
 CLS_LOSS = "SigmoidFocalClassificationLoss"
 REG_LOSSES = ("WeightedSmoothL1Loss", "WeightedL1Loss")
@@ -33,40 +34,10 @@ PARTS = ("get_cls_layer_loss", "get_box_reg_layer_loss")   # an override of eith
 _ORIGINAL = {}   # class -> the get_loss that bind() replaced on it (None: it had none of its own)
 
 
-def _get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
-
-
-class AnchorLossFunction(torch.autograd.Function):
+class AnchorLossFunction(HeadLossFunction):
     """(cls_preds, box_preds, dir_preds or None, labels, reg_targets, anchors, code_weights, scalars, workspace) -> losses (4):
-    [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss].  Only element 3, rpn_loss, carries a gradient: backward scales the
-    unit gradients kept by forward with the upstream gradient of that element, in place, so it runs once."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, code_weights, scalars, workspace):
-        from .. import ops
-        losses, grads = ops.anchor_loss(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, code_weights,
-                                        want_grad=True, workspace=workspace, **scalars)
-        ctx.unit_grads = grads
-        ctx.shapes = (cls_preds.shape, box_preds.shape, None if dir_preds is None else dir_preds.shape)
-        return losses
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_losses):
-        from .. import ops
-        grads = ctx.unit_grads
-        if grads is None:
-            raise RuntimeError("the anchor loss was differentiated a second time: its gradient buffers were scaled in place")
-        ctx.unit_grads = None
-        upstream = grad_losses.contiguous()[3:4]
-        if upstream.dtype != torch.float32:
-            upstream = upstream.float()
-        ops.anchor_loss_backward(grads, upstream)
-        out = tuple(None if g is None else g.view(s) for g, s in zip(grads, ctx.shapes))
-        return out + (None,) * 6
+    [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss]"""
+    OPS, PREDS, WORD = ("anchor_loss", "anchor_loss_backward"), (0, 1, 2), "anchor"
 
 
 def _flat_anchors(head):
@@ -87,35 +58,12 @@ def _flat_anchors(head):
     return flat
 
 
-def _buffers(head, dev, B, N):
-    """the workspace and the pinned table kept on `head`; a table serves one stream at a time"""
-    from .. import ops
-    need = ops.anchor_loss_workspace_bytes(B, N)
-    ws = getattr(head, "_modest_anchor_loss_workspace", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = head._modest_anchor_loss_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    table = getattr(head, "_modest_anchor_loss_table", None)
-    if table is None:
-        table = head._modest_anchor_loss_table = torch.zeros((4,), dtype=torch.float32).pin_memory()
-    return ws, table
-
-
-def _bound_class(head_type):
-    for c in head_type.__mro__:
-        if c in _ORIGINAL:
-            return c
-    return None
-
-
 def get_loss(self):
     """-> (rpn_loss, tb_dict): rpn_loss a 0-dim device tensor with its gradient function, tb_dict the Python floats
     rpn_loss_cls, rpn_loss_loc, rpn_loss_dir (only with a direction head) and rpn_loss"""
     from .. import ops
-    base = _bound_class(type(self))
-    if base is not None and any(getattr(type(self), part, None) is not getattr(base, part, None) for part in PARTS):
-        original = _ORIGINAL[base]
-        if original is None:
-            original = next(c.__dict__["get_loss"] for c in base.__mro__[1:] if "get_loss" in c.__dict__)
+    _, original = replaced_get_loss(type(self), _ORIGINAL, PARTS)
+    if original is not None:
         return original(self)
     model_cfg = self.model_cfg
     if _get(model_cfg, "USE_MULTIHEAD", False) or getattr(self, "use_multihead", False):
@@ -162,25 +110,17 @@ def get_loss(self):
     labels = labels.reshape(batch_size, -1).contiguous()
     targets = targets.float().reshape(batch_size, -1, targets.shape[-1]).contiguous()
     anchors = _flat_anchors(self)
-    code_weights = getattr(reg_fn, "code_weights", None)
-    if code_weights is None:
-        code_weights = torch.ones((code,), dtype=torch.float32, device=cls.device)
-    elif not torch.is_tensor(code_weights):
-        code_weights = torch.tensor([float(v) for v in code_weights], dtype=torch.float32, device=cls.device)
-    else:
-        code_weights = code_weights.to(device=cls.device, dtype=torch.float32).reshape(-1).contiguous()
+    code_weights = code_weights_tensor(reg_fn, code, cls.device)
     scalars = dict(beta=float(getattr(reg_fn, "beta", 0.0)), dir_offset=float(_get(model_cfg, "DIR_OFFSET", 0.0)) if dirp is not None else 0.0,
                    cls_weight=float(weights['cls_weight']), loc_weight=float(weights['loc_weight']),
                    dir_weight=float(weights['dir_weight']) if dirp is not None else 0.0, alpha=alpha, gamma=gamma)
-    ws, table = _buffers(self, cls.device, batch_size, N)
+    ws, table = buffers(self, "_modest_anchor_loss", ops.anchor_loss_workspace_bytes(batch_size, N), 4, cls.device)
     wants = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (cls, box, dirp))
     if wants:
         losses = AnchorLossFunction.apply(cls, box, dirp, labels, targets, anchors, code_weights, scalars, ws)
     else:
         losses, _ = ops.anchor_loss(cls, box, dirp, labels, targets, anchors, code_weights, want_grad=False, workspace=ws, **scalars)
-    table.copy_(losses.detach(), non_blocking=True)
-    torch.cuda.current_stream(cls.device).synchronize()      # the one host wait
-    values = table.tolist()
+    values = read_table(table, losses, cls.device)
     tb_dict = {'rpn_loss_cls': values[0], 'rpn_loss_loc': values[1]}
     if dirp is not None:
         tb_dict['rpn_loss_dir'] = values[2]

@@ -25,7 +25,8 @@ one replaced.  The dict in ``forward_ret_dict`` is left as found.
 ``bind(cls, terms)`` sets the method on a head class; ``pcdet_bind.bind_point_loss()`` does that for the reference's three.
 """
 import torch
-from torch.autograd.function import once_differentiable
+
+from ._head_loss import HeadLossFunction, _get, buffers, code_weights_tensor, read_table, replaced_get_loss
 
 CLS_LOSS_FUNC = "SigmoidFocalClassificationLoss"
 REG_LOSS_FUNC = "WeightedSmoothL1Loss"
@@ -37,60 +38,10 @@ _ORIGINAL = {}   # class -> the get_loss that bind() replaced on it (None: it ha
 _TERMS = {}      # class -> its terms: "cls", "part", "box", or "box?" (iff the head has box_layers)
 
 
-def _get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
-
-
-class PointLossFunction(torch.autograd.Function):
-    """(cls_preds, part_preds | None, box_preds | None, labels, part_labels, box_labels, code_weights, scalars, workspace) ->
-    table (5): [point_loss_cls, point_loss_part, point_loss_box, point_loss, point_pos_num].  Only element 3, point_loss,
-    carries a gradient: backward scales the unit gradients kept by forward with the upstream gradient of that element, in
-    place, so it runs once."""
-
-    @staticmethod
-    def forward(ctx, cls_preds, part_preds, box_preds, labels, part_labels, box_labels, code_weights, scalars, workspace):
-        from .. import ops
-        table, grads = ops.point_loss(cls_preds, labels, part_preds, part_labels, box_preds, box_labels, code_weights,
-                                      want_grad=True, workspace=workspace, **scalars)
-        ctx.unit_grads = grads
-        ctx.shapes = tuple(None if t is None else t.shape for t in (cls_preds, part_preds, box_preds))
-        return table
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_table):
-        from .. import ops
-        grads = ctx.unit_grads
-        if grads is None:
-            raise RuntimeError("the point-head loss was differentiated a second time: its gradient buffers were scaled in place")
-        ctx.unit_grads = None
-        upstream = grad_table.contiguous()[3:4]
-        if upstream.dtype != torch.float32:
-            upstream = upstream.float()
-        ops.point_loss_backward(grads, upstream)
-        return tuple(None if g is None else g.view(s) for g, s in zip(grads, ctx.shapes)) + (None,) * 6
-
-
-def _buffers(head, dev, N):
-    """the workspace and the pinned table kept on `head`; a table serves one stream at a time"""
-    from .. import ops
-    need = ops.point_loss_workspace_bytes(N)
-    ws = getattr(head, "_modest_point_loss_workspace", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = head._modest_point_loss_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    table = getattr(head, "_modest_point_loss_table", None)
-    if table is None:
-        table = head._modest_point_loss_table = torch.zeros((5,), dtype=torch.float32).pin_memory()
-    return ws, table
-
-
-def _bound_class(head_type):
-    for c in head_type.__mro__:
-        if c in _ORIGINAL:
-            return c
-    return None
+class PointLossFunction(HeadLossFunction):
+    """(cls_preds, labels, part_preds | None, part_labels, box_preds | None, box_labels, code_weights, scalars, workspace) ->
+    table (5): [point_loss_cls, point_loss_part, point_loss_box, point_loss, point_pos_num]"""
+    OPS, PREDS, WORD = ("point_loss", "point_loss_backward"), (0, 2, 4), "point-head"
 
 
 def get_loss(self, tb_dict=None):
@@ -98,11 +49,8 @@ def get_loss(self, tb_dict=None):
     new one) updated with the Python floats point_loss_cls, point_pos_num and, for the terms of the head, point_loss_part and
     point_loss_box -- the reference's keys in the reference's order; no key for the total"""
     from .. import ops
-    base = _bound_class(type(self))
-    if base is not None and any(getattr(type(self), part, None) is not getattr(base, part, None) for part in PARTS):
-        original = _ORIGINAL[base]
-        if original is None:
-            original = next(c.__dict__["get_loss"] for c in base.__mro__[1:] if "get_loss" in c.__dict__)
+    base, original = replaced_get_loss(type(self), _ORIGINAL, PARTS)
+    if original is not None:
         return original(self, tb_dict)
     tb_dict = {} if tb_dict is None else tb_dict
     terms = _TERMS[base] if base is not None else TERMS[type(self).__name__]      # called unbound: by the class's name
@@ -165,13 +113,7 @@ def get_loss(self, tb_dict=None):
         part, part_t = part.reshape(-1, ops.POINT_LOSS_PART), part_t.detach().float().reshape(-1, ops.POINT_LOSS_PART)
     if with_box:
         box, box_t = box.reshape(-1, code), box_t.detach().float().reshape(-1, code)
-        code_weights = getattr(reg_fn, "code_weights", None)
-        if code_weights is None:
-            code_weights = torch.ones((code,), dtype=torch.float32, device=dev)
-        elif not torch.is_tensor(code_weights):
-            code_weights = torch.tensor([float(v) for v in code_weights], dtype=torch.float32, device=dev)
-        else:
-            code_weights = code_weights.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        code_weights = code_weights_tensor(reg_fn, code, dev)
         if code_weights.numel() != code:
             raise ValueError(f"code_weights has {code_weights.numel()} elements, the code size is {code}")
     weights = _get(_get(self.model_cfg, "LOSS_CONFIG"), "LOSS_WEIGHTS")
@@ -179,17 +121,15 @@ def get_loss(self, tb_dict=None):
                    cls_weight=float(weights["point_cls_weight"]),
                    part_weight=float(weights["point_part_weight"]) if with_part else 0.0,
                    box_weight=float(weights["point_box_weight"]) if with_box else 0.0)
-    ws, table = _buffers(self, dev, N)
+    ws, table = buffers(self, "_modest_point_loss", ops.point_loss_workspace_bytes(N), 5, dev)
     preds = [t for t in (cls, part, box) if t is not None]
     if torch.is_grad_enabled() and any(t.requires_grad for t in preds):
-        out = PointLossFunction.apply(cls, part, box, labels, part_t, box_t, code_weights, scalars, ws)
+        out = PointLossFunction.apply(cls, labels, part, part_t, box, box_t, code_weights, scalars, ws)
     else:
         out, _ = ops.point_loss(cls.detach(), labels, None if part is None else part.detach(), part_t,
                                 None if box is None else box.detach(), box_t, code_weights, want_grad=False, workspace=ws,
                                 **scalars)
-    table.copy_(out.detach(), non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()      # the one host wait
-    values = table.tolist()
+    values = read_table(table, out, dev)
     tb_dict["point_loss_cls"] = values[0]
     tb_dict["point_pos_num"] = values[4]
     if with_part:

@@ -25,7 +25,8 @@ One visible difference: the reference clamps the sizes inside ``forward_ret_dict
 ``RoIHeadTemplate``.
 """
 import torch
-from torch.autograd.function import once_differentiable
+
+from ._head_loss import HeadLossFunction, _get, buffers, code_weights_tensor, read_table, replaced_get_loss
 
 CLS_LOSS = "BinaryCrossEntropy"
 REG_LOSS = "smooth-l1"
@@ -36,60 +37,10 @@ PARTS = ("get_box_reg_layer_loss", "get_box_cls_layer_loss")   # an override of 
 _ORIGINAL = {}   # class -> the get_loss that bind() replaced on it (None: it had none of its own)
 
 
-def _get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
-
-
-class RoiLossFunction(torch.autograd.Function):
+class RoiLossFunction(HeadLossFunction):
     """(rcnn_cls, rcnn_reg, labels, mask, gt_of_rois, gt_of_rois_src, rois, code_weights, scalars, workspace) -> table (6):
-    [rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner, rcnn_loss, fg_sum, cls_valid].  Only element 3, rcnn_loss, carries a
-    gradient: backward scales the unit gradients kept by forward with the upstream gradient of that element, in place, so it
-    runs once."""
-
-    @staticmethod
-    def forward(ctx, rcnn_cls, rcnn_reg, labels, mask, gt_of_rois, gt_of_rois_src, rois, code_weights, scalars, workspace):
-        from .. import ops
-        table, grads = ops.roi_loss(rcnn_cls, rcnn_reg, labels, mask, gt_of_rois, gt_of_rois_src, rois, code_weights,
-                                    want_grad=True, workspace=workspace, **scalars)
-        ctx.unit_grads = grads
-        ctx.shapes = (rcnn_cls.shape, rcnn_reg.shape)
-        return table
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_table):
-        from .. import ops
-        grads = ctx.unit_grads
-        if grads is None:
-            raise RuntimeError("the RoI loss was differentiated a second time: its gradient buffers were scaled in place")
-        ctx.unit_grads = None
-        upstream = grad_table.contiguous()[3:4]
-        if upstream.dtype != torch.float32:
-            upstream = upstream.float()
-        ops.roi_loss_backward(grads, upstream)
-        return tuple(g.view(s) for g, s in zip(grads, ctx.shapes)) + (None,) * 8
-
-
-def _buffers(head, dev, R):
-    """the workspace and the pinned table kept on `head`; a table serves one stream at a time"""
-    from .. import ops
-    need = ops.roi_loss_workspace_bytes(R)
-    ws = getattr(head, "_modest_roi_loss_workspace", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = head._modest_roi_loss_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    table = getattr(head, "_modest_roi_loss_table", None)
-    if table is None:
-        table = head._modest_roi_loss_table = torch.zeros((6,), dtype=torch.float32).pin_memory()
-    return ws, table
-
-
-def _bound_class(head_type):
-    for c in head_type.__mro__:
-        if c in _ORIGINAL:
-            return c
-    return None
+    [rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner, rcnn_loss, fg_sum, cls_valid]"""
+    OPS, PREDS, WORD = ("roi_loss", "roi_loss_backward"), (0, 1), "RoI"
 
 
 def _rows(t, code, name):
@@ -109,11 +60,8 @@ def get_loss(self, tb_dict=None):
     new one) updated with the Python floats rcnn_loss_cls, rcnn_loss_reg, rcnn_loss and, iff the corner term is on and there
     is a foreground row, rcnn_loss_corner"""
     from .. import ops
-    base = _bound_class(type(self))
-    if base is not None and any(getattr(type(self), part, None) is not getattr(base, part, None) for part in PARTS):
-        original = _ORIGINAL[base]
-        if original is None:
-            original = next(c.__dict__["get_loss"] for c in base.__mro__[1:] if "get_loss" in c.__dict__)
+    _, original = replaced_get_loss(type(self), _ORIGINAL, PARTS)
+    if original is not None:
         return original(self, tb_dict)
     tb_dict = {} if tb_dict is None else tb_dict
     loss_cfg = _get(self.model_cfg, "LOSS_CONFIG")
@@ -161,27 +109,19 @@ def get_loss(self, tb_dict=None):
     mask = mask.reshape(R).contiguous()
     gt, src = _rows(gt, code, "gt_of_rois"), _rows(src, code, "gt_of_rois_src")
     rois = rois.detach().float().reshape(R, code).contiguous()
-    code_weights = getattr(reg_fn, "code_weights", None)
-    if code_weights is None:
-        code_weights = torch.ones((code,), dtype=torch.float32, device=dev)
-    elif not torch.is_tensor(code_weights):
-        code_weights = torch.tensor([float(v) for v in code_weights], dtype=torch.float32, device=dev)
-    else:
-        code_weights = code_weights.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    code_weights = code_weights_tensor(reg_fn, code, dev)
     weights = _get(loss_cfg, "LOSS_WEIGHTS")
     corner = bool(_get(loss_cfg, "CORNER_LOSS_REGULARIZATION", False))
     scalars = dict(beta=float(getattr(reg_fn, "beta", 1.0 / 9.0)), cls_weight=float(weights['rcnn_cls_weight']),
                    reg_weight=float(weights['rcnn_reg_weight']),
                    corner_weight=float(weights['rcnn_corner_weight']) if corner else 0.0, corner=corner)
-    ws, table = _buffers(self, dev, R)
+    ws, table = buffers(self, "_modest_roi_loss", ops.roi_loss_workspace_bytes(R), 6, dev)
     if torch.is_grad_enabled() and (cls.requires_grad or reg.requires_grad):
         out = RoiLossFunction.apply(cls, reg, labels, mask, gt.detach(), src.detach(), rois, code_weights, scalars, ws)
     else:
         out, _ = ops.roi_loss(cls.detach(), reg.detach(), labels, mask, gt.detach(), src.detach(), rois, code_weights,
                               want_grad=False, workspace=ws, **scalars)
-    table.copy_(out.detach(), non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()      # the one host wait
-    values = table.tolist()
+    values = read_table(table, out, dev)
     tb_dict['rcnn_loss_cls'] = values[0]
     tb_dict['rcnn_loss_reg'] = values[1]
     if corner and values[4] > 0:

@@ -17,6 +17,9 @@ CASES = {
     "n256": c(head=PART, B=1, N=256, seed=307),
     "n257": c(head=PART, B=1, N=257, num_class=3, seed=308),
     "n65537": c(head=PART, B=1, N=65537, pos=0.03, seed=309),
+    # 2049 workgroups: pl_finish keeps 8 rows of 256 partials in flight, so lane 0 alone makes a second trip, whose other 7
+    # rows are past the end; the cls term only, one class
+    "finish2049": c(head=SIMPLE, B=1, N=2048 * 256 + 1, pos=0.03, seed=329),
     # each combination of terms
     "cls": c(head=SIMPLE, B=2, N=130, num_class=3, seed=310),
     "cls_box": c(head=BOX, B=2, N=130, num_class=3, seed=311),

@@ -15,6 +15,9 @@ CASES = {
     "r256": c(B=1, M=256, seed=207),
     "r257": c(B=1, M=257, seed=208),
     "r1040": c(B=1, M=1040, seed=209),
+    # 2049 workgroups: rl_finish keeps 8 rows of 256 partials in flight, so lane 0 alone makes a second trip, whose other 7
+    # rows are past the end; code 7, the corner term off
+    "finish2049": c(B=1, M=2048 * 256 + 1, corner=False, seed=228),
     # B = 3: a sample without foreground, one all foreground, one all ignored; and nothing valid anywhere (max(., 1) twice)
     "b3": c(B=3, M=100, samples=["nofg", "allfg", "ignore"], seed=210),
     "all_ignored": c(B=2, M=70, samples=["ignore", "ignore"], seed=211),

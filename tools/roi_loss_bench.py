@@ -286,7 +286,7 @@ def main():
         grads_y = {k: p.grad.clone() for k, p in preds.items()}
         torch.cuda.synchronize()
         want = seq.restate(inp, cfg)
-        table = roi_head_loss._buffers(head, dev, R)[1]
+        table = head._modest_roi_loss_table
         got = dict(table=np.array([tb_o["rcnn_loss_cls"], tb_o["rcnn_loss_reg"], tb_o.get("rcnn_loss_corner", 0.0), tb_o["rcnn_loss"],
                                    float(table[4]), float(table[5])], dtype=np.float32),
                    grad_cls=grads_o["cls"].view(-1).cpu().numpy(), grad_reg=grads_o["reg"].cpu().numpy())
