@@ -1429,6 +1429,44 @@ int modest_point_loss(int64_t n_rows, int num_class, int code, const float *cls_
 int modest_point_loss_backward(int64_t n_cls, int64_t n_part, int64_t n_box, float *grad_cls_dev, float *grad_part_dev,
                                float *grad_box_dev, const float *upstream_dev, void *stream);
 
+/* ---- a37: box decoding of the three kinds of head (csrc/box_decode.hip) -------------------------------
+ * generate_predicted_boxes of AnchorHeadTemplate, PointHeadTemplate and RoIHeadTemplate over ResidualCoder /
+ * PointResidualCoder .decode_torch.  Each call only enqueues on `stream`: no allocation, no wait on the host, nothing read
+ * back; EVERY output element is written, so the output need not be initialised.  All tensors float32, contiguous but `points`.
+ * Arithmetic: float32, one rounding per operation in the order written here, sqrt and / correctly rounded, exp / sin / cos /
+ * atan2 the double function rounded once, x ** 2 as x * x; the scalars arrive as float32 (Python floats rounded first).
+ * ARGMAX (direction bins and classes): torch's max(dim=-1) on the CPU -- the first index of the maximum, a NaN counts as the
+ * maximum and the first NaN wins.
+ * With an anchor row (xa ya za dxa dya dza ra extras..) and an encoding (xt yt zt dxt dyt dzt rt.. extras..):
+ *   diag = sqrt(dxa dxa + dya dya); xg = xt diag + xa; yg = yt diag + ya; zg = zt dza + za; dxg = exp(dxt) dxa (dy, dz alike);
+ *   an extra column is t + a.
+ * modest_anchor_decode: box_preds (batch, n_anchors, code_in), anchors (n_anchors, cols) read once per row for every sample,
+ *   cols = code_in, or code_in - 1 with sincos; dir_cls_preds (batch, n_anchors, bins) or NULL; boxes (batch, n_anchors, cols).
+ *   rg = rt + ra, or with sincos (encoding columns 6, 7 = cost, sint) atan2(sint + sin ra, cost + cos ra).  With dir_cls_preds:
+ *   label = ARGMAX of the bins, period = float32(2 pi / bins), v = rg - dir_offset,
+ *   rot = v - floor(v / period + dir_limit_offset) period, rg = (rot + dir_offset) + period float(label).
+ * modest_point_decode: box_preds (n_rows, code_in) with columns 6, 7 = cost, sint; points: row i at points + i point_stride,
+ *   three floats (the caller's view point_coords[:, 1:4]); cls_preds (n_rows, num_class); mean_size (num_class, 3) or NULL;
+ *   boxes (n_rows, code_in - 1).  c = ARGMAX of the classes; (dxa dya dza) = mean_size[c] and the expressions above with
+ *   (xa ya za) = the point; without mean_size xg = xt + xa (y, z alike) and dxg = exp(dxt); rg = atan2(sint, cost); an extra
+ *   column is copied.
+ * modest_roi_decode: rois and box_preds (n_rows, code) -> boxes (n_rows, code).  The expressions above against the roi with
+ *   (xa ya za) = 0 (xg = xt diag + 0), rg = rt + ra; then with c = cos ra, s = sin ra:
+ *   x = ((xg c + yg (-s)) + zg 0) + roi x;  y = ((xg s + yg c) + zg 0) + roi y;  z = (((xg 0) + (yg 0)) + zg 1) + roi z
+ *   (the zero terms make an infinite coordinate a NaN in the others, as a matrix product does).
+ * Limits (the call fails and launches nothing): rows (batch n_anchors, n_rows) <= modest_box_decode_max_rows() = 2^31 - 1 (a
+ * row index is an int, element offsets are int64), code <= 16 and >= 7 (8 where the encoding carries cost and sint),
+ * 1 <= bins <= 8, 1 <= num_class <= 32, point_stride >= 3, buffers 4-byte aligned.                                          */
+int64_t modest_box_decode_max_rows(void);
+int modest_anchor_decode(int batch, int64_t n_anchors, int code_in, int sincos, const float *box_preds_dev,
+                         const float *anchors_dev, const float *dir_cls_preds_dev, int bins, float dir_offset,
+                         float dir_limit_offset, float *boxes_dev, void *stream);
+int modest_point_decode(int64_t n_rows, int code_in, int num_class, const float *box_preds_dev, const float *points_dev,
+                        int64_t point_stride, const float *cls_preds_dev, const float *mean_size_dev, float *boxes_dev,
+                        void *stream);
+int modest_roi_decode(int64_t n_rows, int code, const float *rois_dev, const float *box_preds_dev, float *boxes_dev,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,10 @@ SIGNATURES = {
     "modest_point_loss": (C.c_int, [C.c_int64, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP, VP, VP, VP, C.c_float, C.c_float,
                                     C.c_float, C.c_float, VP, VP, VP, VP, VP, C.c_int64, VP]),
     "modest_point_loss_backward": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, VP, VP, VP, VP, VP]),
+    "modest_box_decode_max_rows": (C.c_int64, []),
+    "modest_anchor_decode": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_float, C.c_float, VP, VP]),
+    "modest_point_decode": (C.c_int, [C.c_int64, C.c_int, C.c_int, VP, VP, C.c_int64, VP, VP, VP, VP]),
+    "modest_roi_decode": (C.c_int, [C.c_int64, C.c_int, VP, VP, VP, VP]),
 }
 
 _lib = None

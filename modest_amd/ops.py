@@ -2348,3 +2348,140 @@ def point_loss_backward(grads, upstream: torch.Tensor):
     """modest_point_loss_backward on PyTorch's current stream: the gradient buffers of `point_loss` (grad_part and grad_box
     may be None) times the float32 device scalar `upstream`, IN PLACE, enqueue only.  -> grads"""
     return _loss_backward("modest_point_loss_backward", ("grad_cls", "grad_part", "grad_box"), grads, upstream)
+
+
+# --------------------------------------------------------------------------- box decoding (DESIGN.md section 7s)
+BOX_DECODE_MAX_ROWS = (1 << 31) - 1   # rows per call (B * N for the anchor head): a row index is an int, element offsets int64
+BOX_DECODE_MAX_CODE = 16              # box code columns
+BOX_DECODE_MAX_BINS = 8               # direction bins
+BOX_DECODE_MAX_CLASS = 32             # class columns of a point
+
+
+def _decode_tensors(named, dev=None):
+    for name, t in named:
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, {named[0][0]} on {dev}")
+    return dev
+
+
+def _decode_out(out, shape, dev):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or out.device != dev
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 {tuple(shape)} tensor on {dev}")
+    return out
+
+
+def _decode_code(code: int, low: int, what: str = "code size"):
+    if code < low or code > BOX_DECODE_MAX_CODE:
+        raise ValueError(f"{what} = {code} is outside the limit of {low} .. {BOX_DECODE_MAX_CODE} box columns")
+
+
+def _decode_rows(rows: int, name: str):
+    if rows > BOX_DECODE_MAX_ROWS:
+        raise ValueError(f"{name} has {rows} rows, above the limit of {BOX_DECODE_MAX_ROWS} rows per call")
+
+
+def anchor_decode(box_preds: torch.Tensor, anchors: torch.Tensor, dir_cls_preds: Optional[torch.Tensor] = None, *,
+                  dir_offset: float = 0.0, dir_limit_offset: float = 0.0, sincos: bool = False, out=None) -> torch.Tensor:
+    """modest_anchor_decode on PyTorch's current stream: enqueue only, nothing is read back.
+    box_preds (B, N, code), anchors (N, 7 + C) with code = 7 + C (8 + C with sincos), dir_cls_preds (B, N, bins) or None:
+    contiguous float32 device tensors; the anchors are read once per row for every sample.  The scalars are rounded to float32,
+    as torch rounds a Python scalar that meets a float32 tensor.
+    -> boxes (B, N, 7 + C) float32 (`out` supplies it), every element written"""
+    dev = _decode_tensors((("box_preds", box_preds), ("anchors", anchors), ("dir_cls_preds", dir_cls_preds)))
+    if box_preds.ndim != 3 or anchors.ndim != 2:
+        raise ValueError(f"box_preds {tuple(box_preds.shape)} must be (B, N, code) and anchors {tuple(anchors.shape)} (N, 7 + C)")
+    B, N, code = (int(v) for v in box_preds.shape)
+    _decode_code(code, 8 if sincos else 7)
+    cols = code - 1 if sincos else code
+    if tuple(anchors.shape) != (N, cols):
+        raise ValueError(f"anchors {tuple(anchors.shape)} must be (N, columns) = ({N}, {cols}) for a code size of {code}"
+                         + (" with sincos" if sincos else ""))
+    _decode_rows(B * N, "box_preds")
+    bins = 0
+    if dir_cls_preds is not None:
+        if dir_cls_preds.ndim != 3 or tuple(dir_cls_preds.shape[:2]) != (B, N):
+            raise ValueError(f"dir_cls_preds {tuple(dir_cls_preds.shape)} must be (B, N, bins) = ({B}, {N}, bins)")
+        bins = int(dir_cls_preds.shape[2])
+        if bins < 1 or bins > BOX_DECODE_MAX_BINS:
+            raise ValueError(f"NUM_DIR_BINS = {bins} is outside the limit of 1 .. {BOX_DECODE_MAX_BINS} direction bins")
+    for name, t in (("box_preds", box_preds), ("anchors", anchors), ("dir_cls_preds", dir_cls_preds)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    boxes = _decode_out(out, (B, N, cols), dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        check(load().modest_anchor_decode(B, N, code, int(bool(sincos)), ptr(box_preds), ptr(anchors), ptr(dir_cls_preds), bins,
+                                          float(dir_offset), float(dir_limit_offset), ptr(boxes), _stream()), "modest_anchor_decode")
+    return boxes
+
+
+def point_decode(point_box_preds: torch.Tensor, points: torch.Tensor, point_cls_preds: torch.Tensor,
+                 mean_size: Optional[torch.Tensor] = None, *, out=None) -> torch.Tensor:
+    """modest_point_decode on PyTorch's current stream: enqueue only, nothing is read back.
+    point_box_preds (N, 8 + C) and point_cls_preds (N, K) contiguous; points (N, 3) with unit column stride and any row stride
+    of at least 3 (the view point_coords[:, 1:4] is read in place); mean_size (K, 3) contiguous, or None for use_mean_size =
+    False: float32 device tensors.
+    -> boxes (N, 7 + C) float32 (`out` supplies it), every element written"""
+    dev = _decode_tensors((("point_box_preds", point_box_preds), ("points", points), ("point_cls_preds", point_cls_preds),
+                           ("mean_size", mean_size)))
+    if point_box_preds.ndim != 2 or point_cls_preds.ndim != 2 or points.ndim != 2:
+        raise ValueError(f"point_box_preds {tuple(point_box_preds.shape)}, point_cls_preds {tuple(point_cls_preds.shape)} and "
+                         f"points {tuple(points.shape)} must be (N, 8 + C), (N, K) and (N, 3)")
+    N, code = (int(v) for v in point_box_preds.shape)
+    _decode_code(code, 8)
+    K = int(point_cls_preds.shape[1])
+    if K < 1 or K > BOX_DECODE_MAX_CLASS:
+        raise ValueError(f"num_class = {K} is outside the limit of 1 .. {BOX_DECODE_MAX_CLASS} class columns")
+    _decode_rows(N, "point_box_preds")
+    if int(point_cls_preds.shape[0]) != N:
+        raise ValueError(f"point_cls_preds has {int(point_cls_preds.shape[0])} rows, point_box_preds {N}")
+    if tuple(points.shape) != (N, 3):
+        raise ValueError(f"points {tuple(points.shape)} must be (N, 3) = ({N}, 3)")
+    if N and (points.stride(1) != 1 or (N > 1 and points.stride(0) < 3)):
+        raise ValueError(f"points must have unit column stride and a row stride of at least 3, got strides {tuple(points.stride())}")
+    if mean_size is not None and (tuple(mean_size.shape) != (K, 3) or not mean_size.is_contiguous()):
+        raise ValueError(f"mean_size {tuple(mean_size.shape)} must be a contiguous (num_class, 3) = ({K}, 3)")
+    for name, t in (("point_box_preds", point_box_preds), ("point_cls_preds", point_cls_preds)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    boxes = _decode_out(out, (N, code - 1), dev)
+    stride = int(points.stride(0)) if N > 1 else 3
+    with torch.cuda.device(dev):
+        check(load().modest_point_decode(N, code, K, point_box_preds.data_ptr(), points.data_ptr(), stride,
+                                         point_cls_preds.data_ptr(), mean_size.data_ptr() if mean_size is not None else None,
+                                         boxes.data_ptr(), _stream()), "modest_point_decode")
+    return boxes
+
+
+def roi_decode(rois: torch.Tensor, box_preds: torch.Tensor, *, out=None) -> torch.Tensor:
+    """modest_roi_decode on PyTorch's current stream: enqueue only, nothing is read back.
+    rois (R, code) or (B, M, code) and box_preds (R, code) or (B, M, code), contiguous float32 device tensors with the same
+    number of rows; neither is written.
+    -> boxes (R, code) float32 (`out` supplies it), every element written"""
+    dev = _decode_tensors((("rois", rois), ("box_preds", box_preds)))
+    if rois.ndim < 2 or box_preds.ndim < 2:
+        raise ValueError(f"rois {tuple(rois.shape)} and box_preds {tuple(box_preds.shape)} must be (R, code) or (B, M, code)")
+    code = int(box_preds.shape[-1])
+    _decode_code(code, 7)
+    R = box_preds.numel() // code
+    _decode_rows(R, "box_preds")
+    if int(rois.shape[-1]) != code or rois.numel() != R * code:
+        raise ValueError(f"rois {tuple(rois.shape)} must hold {R} rows of the code size {code}")
+    for name, t in (("rois", rois), ("box_preds", box_preds)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    boxes = _decode_out(out, (R, code), dev)
+    with torch.cuda.device(dev):
+        check(load().modest_roi_decode(R, code, rois.data_ptr(), box_preds.data_ptr(), boxes.data_ptr(), _stream()),
+              "modest_roi_decode")
+    return boxes

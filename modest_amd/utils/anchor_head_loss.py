@@ -24,6 +24,7 @@ One visible difference: with ``num_class == 1`` the reference overwrites the pos
 """
 import torch
 
+from ._anchors import flat_anchors as _flat_anchors
 from ._head_loss import HeadLossFunction, _get, buffers, code_weights_tensor, read_table, replaced_get_loss
 
 CLS_LOSS = "SigmoidFocalClassificationLoss"
@@ -38,24 +39,6 @@ class AnchorLossFunction(HeadLossFunction):
     """(cls_preds, box_preds, dir_preds or None, labels, reg_targets, anchors, code_weights, scalars, workspace) -> losses (4):
     [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss]"""
     OPS, PREDS, WORD = ("anchor_loss", "anchor_loss_backward"), (0, 1, 2), "anchor"
-
-
-def _flat_anchors(head):
-    """(N, cols) anchors of a single head on the device, flattened as the reference flattens them, built once per list of
-    anchor tensors (keyed as modest_amd.utils.target_assigner keys its tables)"""
-    anchors = head.anchors
-    given = list(anchors) if isinstance(anchors, (list, tuple)) else [anchors]
-    key = getattr(head, "_modest_anchor_loss_key", None)
-    if key is not None and len(key) == len(given) and all(a is b and a._version == v for a, (b, v) in zip(given, key)):
-        return head._modest_anchor_loss_anchors
-    if isinstance(anchors, (list, tuple)):
-        flat = torch.cat(given, dim=-3) if len(given) > 1 else given[0]
-    else:
-        flat = anchors
-    flat = flat.reshape(-1, flat.shape[-1]).float().contiguous()
-    head._modest_anchor_loss_anchors = flat
-    head._modest_anchor_loss_key = [(a, a._version) for a in given]
-    return flat
 
 
 def get_loss(self):

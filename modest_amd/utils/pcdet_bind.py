@@ -65,6 +65,11 @@ of the point heads with its gradients in one call -- on `
 ``PointIntraPartOffsetHead`` of ``pcdet.models.dense_heads``, whose modules are imported for it if they are not yet (each
 class defines its own ``get_loss``, so binding the template would do nothing); a head that overrides
 ``get_cls_layer_loss``, ``get_part_layer_loss`` or ``get_box_layer_loss`` reaches the method that was replaced.
+
+``bind_box_decode()``, a function of its own like the others, sets the three ``generate_predicted_boxes`` of
+``modest_amd.utils.box_decode`` -- the box decoding of every head in one call each -- on
+``AnchorHeadTemplate``, ``PointHeadTemplate`` and ``RoIHeadTemplate``, whose modules are imported for it if they are not yet; a
+head that overrides ``generate_predicted_boxes`` itself keeps its own.  The decoded boxes carry no ``grad_fn``.
 """
 import importlib
 import importlib.util
@@ -106,6 +111,10 @@ POINT_LOSS_NAMES = {"pcdet.models.dense_heads.point_head_box": "PointHeadBox",
                     "pcdet.models.dense_heads.point_head_simple": "PointHeadSimple",
                     "pcdet.models.dense_heads.point_intra_part_head": "PointIntraPartOffsetHead"}
 POINT_LOSS = "modest_amd.utils.point_head_loss"        # its method set on the three classes by bind_point_loss()
+BOX_DECODE_NAMES = {"pcdet.models.dense_heads.anchor_head_template": "AnchorHeadTemplate",
+                    "pcdet.models.dense_heads.point_head_template": "PointHeadTemplate",
+                    "pcdet.models.roi_heads.roi_head_template": "RoIHeadTemplate"}
+BOX_DECODE = "modest_amd.utils.box_decode"             # its methods set on the three templates by bind_box_decode()
 
 
 class StandIn(types.ModuleType):
@@ -310,6 +319,30 @@ def bind_point_loss():
         if head is None:
             continue
         importlib.import_module(POINT_LOSS).bind(head)
+        bound[name] = mod
+    return bound if found else None
+
+
+def bind_box_decode():
+    """AnchorHeadTemplate / PointHeadTemplate / RoIHeadTemplate .generate_predicted_boxes := the three methods of
+    modest_amd.utils.box_decode -- the box decoding of the heads -- in the reference's modules where they
+    are imported or can be -> {module name: module} of the modules bound, or None where pcdet cannot be imported.  A function
+    of its own: install() and what it returns stay as they are.  Only the templates' own methods are set, so a head that
+    overrides generate_predicted_boxes keeps its own.  A module that lacks its class is skipped.  Idempotent; before or after
+    ``import pcdet.models``; touches no GPU state."""
+    bound, found = {}, False
+    for name, cls_name in BOX_DECODE_NAMES.items():
+        mod = sys.modules.get(name)
+        if mod is None:
+            try:
+                mod = importlib.import_module(name)
+            except ImportError:
+                continue      # no pcdet on the path (or one that does not import here): nothing to bind onto
+        found = True
+        head = getattr(mod, cls_name, None)
+        if head is None:
+            continue
+        importlib.import_module(BOX_DECODE).bind(head, cls_name)
         bound[name] = mod
     return bound if found else None
 
