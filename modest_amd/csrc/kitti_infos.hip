@@ -27,6 +27,7 @@
 //   box table (no device libm reproduces them); the three comparisons in double, MARGIN = (float)1e-2.
 //   Hull predicate: float64 margin of the point against the ideal box, m = min(dx/2-|lx|, dy/2-|ly|, dz/2-|lz|);
 //   m >= tau inside, m <= -tau outside, else undecided and left to the host's Delaunay (modest_amd/kitti_infos.py).
+//   A NaN coordinate makes m a NaN: neither inside nor undecided.  The extents come without their sign (_box_table).
 //
 // A cheap float32 test discards a (row, box) pair before either predicate: max(|x-cx|, |y-cy|) > reject, where the
 // host sets reject above the half diagonal of the box footprint plus both margins plus the rounding of the float32
@@ -102,6 +103,10 @@ __device__ __forceinline__ double hull_margin(const float4 p, const modest_infos
     const double lx = fma(sy, B.cs[1], sx * B.cs[0]);
     const double ly = fma(sy, B.cs[0], -(sx * B.cs[1]));
     const double mx = B.b[3] * 0.5 - fabs(lx), my = B.b[4] * 0.5 - fabs(ly), mz = B.b[5] * 0.5 - fabs(sz);
+    // a row with a NaN coordinate is neither inside nor undecided (Delaunay.find_simplex answers -1 for it): its margin
+    // is a NaN, which fails both comparisons.  fmin alone hands back the operand that is not a NaN, the margin of the
+    // other axes (and the reject test's fmaxf lets such a row through, which keeps that test conservative).
+    if (mx != mx || my != my || mz != mz) return mx + my + mz;
     return fmin(mx, fmin(my, mz));
 }
 

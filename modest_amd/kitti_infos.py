@@ -234,8 +234,10 @@ def points_in_boxes_host(points, boxes):
 
 
 def box_margin64(points, box7):
-    """distance-like margin of float32 points against the ideal float64 box: min over the axes of half extent - |local|"""
-    b = np.asarray(box7, dtype=np.float64)
+    """distance-like margin of float32 points against the ideal float64 box: min over the axes of half extent - |local|
+    (the extents without their sign, as _box_table hands them to the device)"""
+    b = np.array(box7, dtype=np.float64)
+    b[3:6] = np.abs(b[3:6])
     p = np.asarray(points, dtype=np.float64)
     sx, sy, sz = p[:, 0] - b[0], p[:, 1] - b[1], p[:, 2] - b[2]
     c, s = np.cos(b[6]), np.sin(b[6])
@@ -431,6 +433,10 @@ def _box_table(gt_boxes, corners):
     b64 = np.ascontiguousarray(gt_boxes, dtype=np.float64)
     b32 = b64.astype(np.float32)
     t["b"], t["bf"] = b64, b32
+    # the hull test sees the extents without their sign: the eight corners of a box with a negative size are those of
+    # the box with its absolute value, and the reference counts the points inside their hull (bf, which the database
+    # predicate reads, keeps the sign: |local| < negative / 2 + MARGIN holds for no point, as in the reference)
+    t["b"][:, 3:6] = np.abs(b64[:, 3:6])
     t["cs"][:, 0], t["cs"][:, 1] = np.cos(b64[:, 6]), np.sin(b64[:, 6])
     t["cosa"], t["sina"] = host_cos_sin_f32(b32[:, 6])
     tau = np.array([hull_tau(corners[k]) for k in range(nb)])
