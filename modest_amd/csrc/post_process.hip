@@ -2,11 +2,11 @@
 // pcdet/models/detectors/detector3d_template.py:175-325, over class_agnostic_nms, model_utils/model_nms_utils.py:6-25, and
 // generate_recall_record, with MULTI_CLASSES_NMS off), hand-written for gfx950.  One entry point (include/modest_hip.h,
 // "a33") takes a whole batch, dense or stacked: no context, no device allocation, one stream synchronise at the end, nothing
-// read back but the caller's small pinned table, which the kernels write.  DESIGN.md section 7o.  The keys' helpers,
-// sort64's workspace and the walk (walk_segment, the body of prop_walk too) are those of the RoI proposal layer
+// read back but the caller's small pinned table, which the kernels write.  DESIGN.md section 7o.  The shared argument
+// checks, the keys kernel (rank_keys, here SCORED: the sigmoid of a logit, the double function rounded once, and the score
+// threshold: a row that fails  score >= thresh  (a NaN fails) gets sample B and sorts behind every segment), the host front
+// that ranks the rows and the walk (walk_segment, the body of prop_walk too) are those of the RoI proposal layer
 // (csrc/prop_walk.h); this file adds:
-//   post_keys     prop_keys with the sigmoid of a logit (the double function rounded once) and the score threshold: a row
-//               that fails  score >= thresh  (a NaN fails) gets sample B and sorts behind every segment;
 //   post_walk     walk_segment, then the n survivors' 7 + C columns, scores and labels into the front of the sample's padded
 //               row, and n into the workspace and the caller's pinned table;
 //   post_recall   one workgroup per sample and box list, only with gts: the trim of rt_match, a lane per valid gt (64 at a
@@ -27,22 +27,6 @@
 namespace {
 
 using modest::loss::sigmoid_f32;   // torch.sigmoid's value by the project's rule for log / cos / sin: the double function, rounded once
-
-// prop_keys on the NORMALISED score, with the score threshold: a row that fails  score >= thresh  (a NaN fails) is in no sample
-__global__ __launch_bounds__(256) void post_keys(int64_t n, int b, int64_t rows_per_sample, const float *__restrict__ cls,
-                                               int k, const void *__restrict__ bidx, int kind, int normalized,
-                                               int has_thresh, float thresh, uint64_t *__restrict__ key,
-                                               uint32_t *__restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int label;
-    float s = row_max(cls + i * k, k, label);
-    if (!normalized) s = sigmoid_f32(s);
-    int64_t sample = row_sample(i, b, rows_per_sample, bidx, kind);
-    if (has_thresh && !(s >= thresh)) sample = b;
-    key[i] = ((uint64_t)sample << 32) | descending_bits(s);
-    idx[i] = (uint32_t)i;
-}
 
 // ------------------------------------------------------------------------------------------------ post-processing ("a33")
 constexpr int PR_WAVES = 4;                  // wavefronts of a recall workgroup: each owns a PolyLds
@@ -228,20 +212,11 @@ extern "C" int modest_post_process(int64_t n_rows, int batch_size, int64_t rows_
                                    const float *recall_thresh_host, float *pred_boxes_dev, float *pred_scores_dev,
                                    int64_t *pred_labels_dev, int32_t *table_pinned_host, void *workspace_dev,
                                    int64_t workspace_bytes, void *stream) {
-    MODEST_REQUIRE(n_rows >= 0 && n_rows <= 2147483647LL, "between 0 and 2^31 - 1 rows");
-    MODEST_REQUIRE(batch_size >= 0 && batch_size <= WK_MAX_BATCH, "batch_size at most 65535 (16 sample bits of the sort key)");
-    MODEST_REQUIRE(post_maxsize >= 0 && post_maxsize <= WK_POST_MAX, "NMS_POST_MAXSIZE at most 1024 (the kept list held in LDS)");
-    MODEST_REQUIRE(pre_maxsize >= 0, "NMS_PRE_MAXSIZE is negative");
-    MODEST_REQUIRE(box_cols >= 7 && box_cols <= 4096 && cls_cols >= 1 && cls_cols <= 4096, "7 + C box columns and K >= 1 class columns, 4096 at most");
+    WALK_REQUIRE_SIZES();
     MODEST_REQUIRE(n_thresh >= 0 && n_thresh <= PR_MAX_THRESH, "RECALL_THRESH_LIST of at most 16 thresholds (they travel in the kernel's arguments)");
-    MODEST_REQUIRE(batch_index_kind >= BIDX_NONE && batch_index_kind <= BIDX_I32, "batch_index kind: 0 none, 1 float32, 2 int64, 3 int32");
-    MODEST_REQUIRE(batch_index_kind == BIDX_NONE ? batch_index_dev == nullptr : (batch_index_dev != nullptr || n_rows == 0),
-                   "batch_index and its kind disagree");
-    if (batch_index_kind == BIDX_NONE) {
-        MODEST_REQUIRE(rows_per_sample >= 0 && rows_per_sample * batch_size == n_rows, "dense form: n_rows = batch_size * rows_per_sample");
-    } else {
+    WALK_REQUIRE_BATCH_INDEX();
+    if (batch_index_kind != BIDX_NONE)
         MODEST_REQUIRE(labels_dev == nullptr && n_rois < 0, "given labels and rois need the dense form");
-    }
     MODEST_REQUIRE(n_rois >= -1, "n_rois: -1 without rois");
     MODEST_REQUIRE(with_gt || n_rois < 0, "rois without gts");
     if (with_gt) {
@@ -258,44 +233,23 @@ extern "C" int modest_post_process(int64_t n_rows, int batch_size, int64_t rows_
     MODEST_REQUIRE(table_pinned_host, "NULL table");
     MODEST_REQUIRE(post_maxsize == 0 || (pred_boxes_dev && pred_scores_dev && pred_labels_dev), "NULL output");
     MODEST_REQUIRE(n_rows == 0 || (box_dev && cls_dev), "NULL buffer");
-    const Layout L = layout(n_rows);
     MODEST_REQUIRE(workspace_dev && workspace_bytes >= (int64_t)post_total(n_rows, batch_size),
                    "workspace smaller than modest_post_process_workspace_bytes");
     MODEST_REQUIRE(((uintptr_t)workspace_dev & 7) == 0, "workspace not 8-byte aligned");
     hipStream_t st = as_stream(stream);
-    char *ws = static_cast<char *>(workspace_dev);
     PostParams p;
-    p.w.n = n_rows;
-    p.w.key = nullptr;
-    p.w.idx = nullptr;
+    p.w = walk_params(n_rows, box_dev, box_cols, cls_dev, cls_cols, pre_maxsize, post_maxsize, nms_thresh, pred_boxes_dev,
+                      pred_scores_dev, pred_labels_dev);
     if (n_rows > 0) {
-        uint64_t *key[2] = {reinterpret_cast<uint64_t *>(ws + L.key[0]), reinterpret_cast<uint64_t *>(ws + L.key[1])};
-        uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(ws + L.idx[0]), reinterpret_cast<uint32_t *>(ws + L.idx[1])};
-        uint32_t *table = reinterpret_cast<uint32_t *>(ws + L.table);
-        post_keys<<<(unsigned)((n_rows + 255) / 256), 256, 0, st>>>(n_rows, batch_size, rows_per_sample, cls_dev, cls_cols,
-                                                                batch_index_dev, batch_index_kind, normalized,
-                                                                has_score_thresh, score_thresh, key[0], idx[0]);
-        MODEST_HIP_CHECK(hipGetLastError());
         // the sample field holds batch_size itself for a row below the threshold or of no sample
-        const int bits = 32 + sort64_bit_length((uint64_t)batch_size);
-        const int fin = sort64(key, idx, (int)n_rows, bits, table, st);
-        p.w.key = key[fin];
-        p.w.idx = idx[fin];
+        const int rc = rank_rows<true>(p.w, batch_size, rows_per_sample, batch_index_dev, batch_index_kind, normalized,
+                                       has_score_thresh, score_thresh, batch_size, workspace_dev, st);
+        if (rc != MODEST_OK) return rc;
     }
-    p.w.box = box_dev;
-    p.w.cls = cls_dev;
-    p.w.box_cols = box_cols;
-    p.w.cls_cols = cls_cols;
-    p.w.pre = pre_maxsize;
-    p.w.post = post_maxsize;
-    p.w.thresh = nms_thresh;
-    p.w.rois = pred_boxes_dev;
-    p.w.scores = pred_scores_dev;
-    p.w.labels = pred_labels_dev;
     p.normalized = normalized;
     p.raw_out = output_raw_score;
     p.given = labels_dev;
-    p.nb = reinterpret_cast<int32_t *>(ws + L.total);
+    p.nb = reinterpret_cast<int32_t *>(static_cast<char *>(workspace_dev) + layout(n_rows).total);
     p.table = table_pinned_host;
     p.stride = 2 + 2 * n_thresh;
     if (rotated)

@@ -1,13 +1,16 @@
 // What the RoI proposal layer (csrc/proposals.hip) and the post-processing (csrc/post_process.hip,
-// section 7o) share: the score and sort key of a row, the sample of a row, the workspace of the sort, and the walk of one
-// sample's candidates by a workgroup -- walk_segment, the body of prop_walk and of post_walk, so that both make the same
-// decisions in the same order.  Include from a translation unit built with -ffp-contract=off, after common.h.
+// section 7o) share: the argument checks of the two entry points (WALK_REQUIRE_*), the keys kernel (rank_keys: the score and
+// sort key of a row, the sample of a row), the host front that ranks the rows (walk_params, rank_rows: the workspace of the
+// sort, the keys, the sort), and the walk of one sample's candidates by a workgroup -- walk_segment, the body of prop_walk
+// and of post_walk, so that both make the same decisions in the same order.  The tails of the two walk kernels are their
+// files' own.  Include from a translation unit built with -ffp-contract=off, after common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "iou_bev.h"
 #include "sort64.h"
+#include "loss_terms.h"
 
 namespace {
 
@@ -21,6 +24,21 @@ constexpr int WK_MAX_BATCH = 65535;          // 16 sample bits above the 32 scor
 //                 = 126.5 KB of the CU's 160 KB; a fifth PolyLds would fit, a sixth would not.
 
 enum { BIDX_NONE = 0, BIDX_F32 = 1, BIDX_I64 = 2, BIDX_I32 = 3 };
+
+// The checks modest_proposals and modest_post_process make of the arguments they share, under the names both give them.
+// Macros, not a function: MODEST_REQUIRE reports the entry point it stands in and the condition as it is written here.
+#define WALK_REQUIRE_SIZES()                                                                                                   \
+    MODEST_REQUIRE(n_rows >= 0 && n_rows <= 2147483647LL, "between 0 and 2^31 - 1 rows");                                      \
+    MODEST_REQUIRE(batch_size >= 0 && batch_size <= WK_MAX_BATCH, "batch_size at most 65535 (16 sample bits of the sort key)"); \
+    MODEST_REQUIRE(post_maxsize >= 0 && post_maxsize <= WK_POST_MAX, "NMS_POST_MAXSIZE at most 1024 (the kept list held in LDS)"); \
+    MODEST_REQUIRE(pre_maxsize >= 0, "NMS_PRE_MAXSIZE is negative");                                                           \
+    MODEST_REQUIRE(box_cols >= 7 && box_cols <= 4096 && cls_cols >= 1 && cls_cols <= 4096, "7 + C box columns and K >= 1 class columns, 4096 at most")
+#define WALK_REQUIRE_BATCH_INDEX()                                                                                             \
+    MODEST_REQUIRE(batch_index_kind >= BIDX_NONE && batch_index_kind <= BIDX_I32, "batch_index kind: 0 none, 1 float32, 2 int64, 3 int32"); \
+    MODEST_REQUIRE(batch_index_kind == BIDX_NONE ? batch_index_dev == nullptr : (batch_index_dev != nullptr || n_rows == 0),   \
+                   "batch_index and its kind disagree");                                                                       \
+    if (batch_index_kind == BIDX_NONE)                                                                                         \
+    MODEST_REQUIRE(rows_per_sample >= 0 && rows_per_sample * batch_size == n_rows, "dense form: n_rows = batch_size * rows_per_sample")
 
 // max over the k class values of a row and its column: the lowest column among equal maxima, a NaN above every number
 // (the first NaN wins)
@@ -63,6 +81,27 @@ __device__ __forceinline__ int64_t row_sample(int64_t i, int b, int64_t rows_per
         if (v >= 0 && v < b) sample = v;
     }
     return sample;
+}
+
+// One lane per row: its score, its sample and the 64-bit key  sample << 32 | descending(score) , whose ascending order is the
+// samples one after the other, each by descending score with NaN first.  SCORED (the post-processing): the score is the
+// sigmoid of the class maximum (the double function rounded once) unless `normalized`, and with `has_thresh` a row that
+// fails  score >= thresh  (a NaN fails) is in no sample: it gets sample b and sorts behind every segment.  Not SCORED (the
+// proposal layer): the class maximum as it is, and the three arguments are not read.
+template <bool SCORED>
+__global__ __launch_bounds__(256) void rank_keys(int64_t n, int b, int64_t rows_per_sample, const float *__restrict__ cls,
+                                                 int k, const void *__restrict__ bidx, int kind, int normalized,
+                                                 int has_thresh, float thresh, uint64_t *__restrict__ key,
+                                                 uint32_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int label;
+    float s = row_max(cls + i * k, k, label);
+    if (SCORED && !normalized) s = modest::loss::sigmoid_f32(s);
+    int64_t sample = row_sample(i, b, rows_per_sample, bidx, kind);
+    if (SCORED && has_thresh && !(s >= thresh)) sample = b;
+    key[i] = ((uint64_t)sample << 32) | descending_bits(s);
+    idx[i] = (uint32_t)i;
 }
 
 struct WalkParams {
@@ -216,6 +255,47 @@ Layout layout(int64_t n) {
     L.table = take(4 * sort64_table_words((int64_t)rows));
     L.total = off;
     return L;
+}
+
+// the fields both walks read, the rows not yet ranked
+WalkParams walk_params(int64_t n_rows, const float *box, int box_cols, const float *cls, int cls_cols, int pre, int post,
+                       float thresh, float *rois, float *scores, int64_t *labels) {
+    WalkParams p;
+    p.n = n_rows;
+    p.key = nullptr;
+    p.idx = nullptr;
+    p.box = box;
+    p.cls = cls;
+    p.box_cols = box_cols;
+    p.cls_cols = cls_cols;
+    p.pre = pre;
+    p.post = post;
+    p.thresh = thresh;
+    p.rois = rois;
+    p.scores = scores;
+    p.labels = labels;
+    return p;
+}
+
+// The p.n > 0 rows ranked: key[2] / idx[2] / table laid over the workspace (layout(p.n) bytes, 8-byte aligned: the caller has
+// checked both), rank_keys<SCORED>, sort64 over the 32 score bits and the bits of `sample_max`, the largest value the sample
+// field can hold (it decides the number of radix passes); p.key / p.idx are the sorted side.  -> MODEST_OK or an error code
+template <bool SCORED>
+int rank_rows(WalkParams &p, int batch_size, int64_t rows_per_sample, const void *batch_index_dev, int batch_index_kind,
+              int normalized, int has_thresh, float thresh, int sample_max, void *workspace_dev, hipStream_t st) {
+    const Layout L = layout(p.n);
+    char *ws = static_cast<char *>(workspace_dev);
+    uint64_t *key[2] = {reinterpret_cast<uint64_t *>(ws + L.key[0]), reinterpret_cast<uint64_t *>(ws + L.key[1])};
+    uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(ws + L.idx[0]), reinterpret_cast<uint32_t *>(ws + L.idx[1])};
+    uint32_t *table = reinterpret_cast<uint32_t *>(ws + L.table);
+    rank_keys<SCORED><<<(unsigned)((p.n + 255) / 256), 256, 0, st>>>(p.n, batch_size, rows_per_sample, p.cls, p.cls_cols,
+                                                                   batch_index_dev, batch_index_kind, normalized, has_thresh,
+                                                                   thresh, key[0], idx[0]);
+    MODEST_HIP_CHECK(hipGetLastError());
+    const int fin = sort64(key, idx, (int)p.n, 32 + sort64_bit_length((uint64_t)sample_max), table, st);
+    p.key = key[fin];
+    p.idx = idx[fin];
+    return MODEST_OK;
 }
 
 }  // namespace

@@ -44,6 +44,91 @@ def _np_ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """the address of a tensor's data; None for None"""
+    return t.data_ptr() if t is not None else None
+
+
+def _ptr_filled(t: Optional[torch.Tensor]) -> Optional[int]:
+    """the address of a tensor's data; None for None and for a tensor without elements"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+# --------------------------------------------------------------------------- what the detector ops do with their arguments
+def _device_tensors(named, dtypes=None, optional=(), dtype_error=ValueError, same_device=False):
+    """The loop a detector op opens with, over `named` = ((name, tensor), ...) in the order in which they are refused: each
+    must be a device tensor, and then of float32, or of one of the types `dtypes` ({name: tuple}) gives its name; another
+    type raises `dtype_error` (None: types are not looked at).  A None is passed over for a name among `optional`.
+    same_device: each must also lie on the device of the first.  -> that device"""
+    dev = None
+    for name, t in named:
+        if t is None and name in optional:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+        if dtype_error is not None:
+            allowed = (dtypes or {}).get(name, (torch.float32,))
+            if t.dtype not in allowed:
+                *head, last = (str(d).replace("torch.", "") for d in allowed)
+                raise dtype_error(f"{name} must be {', '.join(head) + ' or ' + last if head else last}, got {t.dtype}")   # "int32, int64 or float32"
+        dev = t.device if dev is None else dev
+        if same_device and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, {named[0][0]} on {dev}")
+    return dev
+
+
+def _outputs(want, out, dev, anchor=None, absent=None):
+    """The output buffers of a call.  `want`: (name, dtype, shape, due) per buffer.  out None: new ones on `dev`, None where
+    none is due.  Else `out` must hold as many entries; one that is not due must be None and one that is due a tensor, refused
+    as "out <name> " + `absent`[0] / `absent`[1] (absent None: every buffer is due and its presence is not looked at); a
+    tensor must pass `_dev` as "out <name>" and have the shape and the device, refused in two messages that name the device
+    of the argument `anchor`, or, without an anchor, in one.  -> the buffers"""
+    if out is None:
+        return [torch.empty(shape, dtype=dtype, device=dev) if due else None for _, dtype, shape, due in want]
+    if len(out) != len(want):
+        raise ValueError(f"out must be ({', '.join(name for name, _, _, _ in want)})")
+    for t, (name, dtype, shape, due) in zip(out, want):
+        if absent is not None:
+            if not due and t is not None:
+                raise ValueError(f"out {name} {absent[0]}")
+            if due and not torch.is_tensor(t):
+                raise ValueError(f"out {name} {absent[1]}")
+            if not due:
+                continue
+        _dev(t, dtype, f"out {name}")
+        if anchor is None:
+            if tuple(t.shape) != shape or t.device != dev:
+                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
+            continue
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.device != dev:
+            raise ValueError(f"out {name} is on {t.device}, {anchor} on {dev}")
+    return out
+
+
+def _workspace(nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
+    """`workspace` if it holds `nbytes` on `dev`, else a new one: an uint8 device tensor either way"""
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    return _dev(workspace, torch.uint8, "workspace")
+
+
+def _workspace_bytes(fn_name: str, *ints) -> int:
+    """the library's `fn_name`(ints): the bytes of a workspace, or the library's refusal raised"""
+    nb = int(getattr(load(), fn_name)(*(int(a) for a in ints)))
+    if nb < 0:
+        check(nb, fn_name)
+    return nb
+
+
+def _cfg_get(cfg, name, *default):
+    """cfg[name] of a dict, cfg.name of anything else; `default` where it is absent"""
+    if isinstance(cfg, dict):
+        return cfg.get(name, *default) if default else cfg[name]
+    return getattr(cfg, name, *default)
+
+
 # --------------------------------------------------------------------------- PP score
 def pp_count(live_xyz: torch.Tensor, hist_xyz: torch.Tensor, trav_offsets: Sequence[int],
              radius: float = 0.3, ctx: Optional[Context] = None) -> torch.Tensor:
@@ -1050,10 +1135,7 @@ def voxelize_workspace_bytes(n_rows: int, batch_size: int, grid_size) -> int:
     """scratch bytes of `voxelize` for n_rows stacked rows: does not depend on the grid (which is only checked)"""
     g = np.ascontiguousarray(grid_size, dtype=np.int32)
     assert g.shape == (3,)
-    nb = int(load().modest_voxelize_workspace_bytes(int(n_rows), int(batch_size), _np_ptr(g)))
-    if nb < 0:
-        check(nb, "modest_voxelize_workspace_bytes")
-    return nb
+    return _workspace_bytes("modest_voxelize_workspace_bytes", n_rows, batch_size, _np_ptr(g))
 
 
 class VoxelizeGeometry:
@@ -1086,10 +1168,7 @@ def voxelize_plan(points: torch.Tensor, voxel_size, point_cloud_range, max_num_p
     if cap < 1:
         raise ValueError("batch_size must be positive")
     dev = points.device
-    nbytes = voxelize_workspace_bytes(pl.n, cap, geo.grid32)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    pl.workspace = _dev(workspace, torch.uint8, "workspace")
+    pl.workspace = workspace = _workspace(voxelize_workspace_bytes(pl.n, cap, geo.grid32), workspace, dev)
     if counts_pinned is None or counts_pinned.numel() < 4 + cap:
         counts_pinned = torch.empty((4 + cap,), dtype=torch.int32).pin_memory()
     if counts_pinned.dtype != torch.int32 or not counts_pinned.is_pinned():
@@ -1205,12 +1284,7 @@ def spconv_rulebook(indices: torch.Tensor, batch_size: int, spatial_shape, kerne
     dev = indices.device
     lib = load()
     geo = [np.ascontiguousarray(v, dtype=np.int32) for v in (rb.in_shape, rb.kernel, rb.stride, rb.padding)]
-    nbytes = int(lib.modest_spconv_rulebook_workspace_bytes(rb.n_in, rb.kvol, int(rb.subm)))
-    if nbytes < 0:
-        check(nbytes, "modest_spconv_rulebook_workspace_bytes")
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    workspace = _workspace(_workspace_bytes("modest_spconv_rulebook_workspace_bytes", rb.n_in, rb.kvol, rb.subm), workspace, dev)
     if counts_pinned is None:
         counts_pinned = torch.zeros((2,), dtype=torch.int32).pin_memory()
     if counts_pinned.dtype != torch.int32 or not counts_pinned.is_pinned() or counts_pinned.numel() < 2:
@@ -1304,9 +1378,7 @@ def spconv_backward(features: torch.Tensor, weight: torch.Tensor, grad_out: torc
             dw = given(grad_weight, tuple(weight.shape), "grad_weight")
             if need_bias_grad:
                 db = given(grad_bias, (cout,), "grad_bias")
-            nbytes = int(lib.modest_spconv_wgrad_workspace_bytes(rb.n_out, rb.kvol, cin, cout))
-            if nbytes < 0:
-                check(nbytes, "modest_spconv_wgrad_workspace_bytes")
+            nbytes = _workspace_bytes("modest_spconv_wgrad_workspace_bytes", rb.n_out, rb.kvol, cin, cout)
             ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
             SPCONV_CALLS["weight_grad"] += 1
             check(lib.modest_spconv_wgrad(features.data_ptr(), rb.n_in, cin, grad_out.data_ptr(), rb.n_out, cout,
@@ -1347,9 +1419,7 @@ def spconv_class_order(rb: SpconvRulebook):
     dev = rb.indices.device
     lib = load()
     classes = spconv_classes(rb)
-    nbytes = int(lib.modest_spconv_class_order_workspace_bytes(rb.n_in, classes))
-    if nbytes < 0:
-        check(nbytes, "modest_spconv_class_order_workspace_bytes")
+    nbytes = _workspace_bytes("modest_spconv_class_order_workspace_bytes", rb.n_in, classes)
     stride, pad = (np.ascontiguousarray(v, dtype=np.int32) for v in (rb.stride, rb.padding))
     with torch.cuda.device(dev):
         ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
@@ -1438,9 +1508,7 @@ def spconv_inverse_backward(features: torch.Tensor, weight: torch.Tensor, grad_o
                                                 None, rb.nbr.data_ptr(), rb.n_out, dx.data_ptr(), _stream()),
                   "modest_spconv_gather_gemm")
         if need_weight_grad:
-            nbytes = int(lib.modest_spconv_wgrad_workspace_bytes(rb.n_out, rb.kvol, cout, cin))
-            if nbytes < 0:
-                check(nbytes, "modest_spconv_wgrad_workspace_bytes")
+            nbytes = _workspace_bytes("modest_spconv_wgrad_workspace_bytes", rb.n_out, rb.kvol, cout, cin)
             ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
             dwt = torch.empty((rb.kvol, cout, cin), dtype=torch.float32, device=dev)
             SPCONV_INVERSE_CALLS["weight_grad"] += 1
@@ -1455,10 +1523,7 @@ def spconv_inverse_backward(features: torch.Tensor, weight: torch.Tensor, grad_o
 
 # --------------------------------------------------------------------------- anchor target assignment
 def anchor_targets_workspace_bytes(batch_size: int, n_cls: int, m: int) -> int:
-    nb = int(load().modest_anchor_targets_workspace_bytes(int(batch_size), int(n_cls), int(m)))
-    if nb < 0:
-        check(nb, "modest_anchor_targets_workspace_bytes")
-    return nb
+    return _workspace_bytes("modest_anchor_targets_workspace_bytes", batch_size, n_cls, m)
 
 
 def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Tensor, thresholds: torch.Tensor,
@@ -1488,23 +1553,9 @@ def anchor_targets(gt: torch.Tensor, anchors: torch.Tensor, cls_table: torch.Ten
         raise ValueError("cls_table (n_cls, 5), thresholds (n_cls, 2) and name_match (n_cls, n_names) disagree")
     dev = gt.device
     code = 7 + int(bool(sincos)) + min(A - 7, G - 8)
-    want = (("labels", torch.int32, (B, int(n_out))), ("targets", torch.float32, (B, int(n_out), code)),
-            ("weights", torch.float32, (B, int(n_out))))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
-    if len(out) != 3:
-        raise ValueError("out must be (labels, targets, weights)")
-    for t, (name, dtype, shape) in zip(out, want):
-        _dev(t, dtype, f"out {name}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
-        if t.device != dev:
-            raise ValueError(f"out {name} is on {t.device}, gt on {dev}")
-    labels, targets, weights = out
-    nbytes = anchor_targets_workspace_bytes(B, n_cls, M)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    labels, targets, weights = _outputs((("labels", torch.int32, (B, int(n_out)), True), ("targets", torch.float32, (B, int(n_out), code), True),
+                                         ("weights", torch.float32, (B, int(n_out)), True)), out, dev, anchor="gt")
+    workspace = _workspace(anchor_targets_workspace_bytes(B, n_cls, M), workspace, dev)
     sb, sm, sc = (int(v) for v in gt.stride())
     with torch.cuda.device(dev):
         check(lib.modest_anchor_targets(B, M, G, gt.data_ptr(), sb, sm, sc, anchors.data_ptr(), A, n_cls,
@@ -1524,11 +1575,7 @@ def point_targets(points: torch.Tensor, gt_boxes: torch.Tensor, extend_gt_boxes:
     -> point_cls_labels (N) int64, point_box_labels (N, 8) float32 or None, point_part_labels (N, 3) float32 or None:
     freshly allocated, or the three entries of `out` (None where the label is not asked for; else of exactly these shapes
     and types, contiguous, on the points' device), every element of which is written."""
-    for t, name in ((points, "points"), (gt_boxes, "gt_boxes"), (extend_gt_boxes, "extend_gt_boxes")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    _device_tensors((("points", points), ("gt_boxes", gt_boxes), ("extend_gt_boxes", extend_gt_boxes)))
     if points.ndim != 2 or points.shape[1] != 4:
         raise ValueError(f"points has shape {tuple(points.shape)}, expected (N, 4)")
     if gt_boxes.ndim != 3 or gt_boxes.shape[2] != 8 or tuple(extend_gt_boxes.shape) != tuple(gt_boxes.shape):
@@ -1551,25 +1598,9 @@ def point_targets(points: torch.Tensor, gt_boxes: torch.Tensor, extend_gt_boxes:
     B, M = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
     if points.stride(1) != 1:
         points = points.contiguous()
-    want = (("point_cls_labels", torch.int64, (N,), True), ("point_box_labels", torch.float32, (N, 8), bool(want_box)),
-            ("point_part_labels", torch.float32, (N, 3), bool(want_part)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if asked else None for _, dtype, shape, asked in want)
-    if len(out) != 3:
-        raise ValueError("out must be (point_cls_labels, point_box_labels, point_part_labels)")
-    for t, (name, dtype, shape, asked) in zip(out, want):
-        if not asked:
-            if t is not None:
-                raise ValueError(f"out {name} is given but not asked for")
-            continue
-        if not torch.is_tensor(t):
-            raise ValueError(f"out {name} is missing")
-        _dev(t, dtype, f"out {name}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
-        if t.device != dev:
-            raise ValueError(f"out {name} is on {t.device}, points on {dev}")
-    labels, box, part = out
+    labels, box, part = _outputs((("point_cls_labels", torch.int64, (N,), True), ("point_box_labels", torch.float32, (N, 8), bool(want_box)),
+                                  ("point_part_labels", torch.float32, (N, 3), bool(want_part))), out, dev, anchor="points",
+                                 absent=("is given but not asked for", "is missing"))
     if N == 0:
         return labels, box, part   # nothing to write, nothing launched
     lib = load()
@@ -1580,40 +1611,24 @@ def point_targets(points: torch.Tensor, gt_boxes: torch.Tensor, extend_gt_boxes:
                                        gt_boxes.data_ptr() if B and M else None, *gs,
                                        extend_gt_boxes.data_ptr() if B and M else None, *es,
                                        mean_size.data_ptr() if n_mean else None, n_mean, int(num_class), labels.data_ptr(),
-                                       box.data_ptr() if box is not None else None,
-                                       part.data_ptr() if part is not None else None, _stream()), "modest_point_targets")
+                                       _ptr(box), _ptr(part), _stream()), "modest_point_targets")
     return labels, box, part
 
 
 # --------------------------------------------------------------------------- RoI proposal layer
 def proposals_workspace_bytes(n_rows: int) -> int:
-    nb = int(load().modest_proposals_workspace_bytes(int(n_rows)))
-    if nb < 0:
-        check(nb, "modest_proposals_workspace_bytes")
-    return nb
+    return _workspace_bytes("modest_proposals_workspace_bytes", n_rows)
 
 
 _BATCH_INDEX_KINDS = {torch.float32: 1, torch.int64: 2, torch.int32: 3}
 
 
-def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int, pre_maxsize: int, post_maxsize: int,
-              thresh: float, rotated: bool = True, batch_index: Optional[torch.Tensor] = None,
-              workspace: Optional[torch.Tensor] = None, out=None):
-    """modest_proposals on PyTorch's current stream: enqueue only, nothing is read back.
-    Dense form: box_preds (B, N, 7 + C) and cls_preds (B, N, K) float32 with B == batch_size.  Stacked form: (N1 + N2 + ..,
-    7 + C) and (N1 + N2 + .., K) with batch_index (N1 + N2 + ..), a float or integer tensor of sample numbers in any order.
-    Per sample the min(pre_maxsize, rows) highest class maxima (NaN first, equal scores by ascending row, the lowest class
-    among equal maxima) are walked by greedy NMS at `thresh` (rotated: nms_gpu, else nms_normal_gpu) up to the
-    post_maxsize-th survivor.  -> rois (B, post_maxsize, 7 + C) float32, roi_scores (B, post_maxsize) float32, roi_labels
-    (B, post_maxsize) int64 (label + 1; 1 in the padding): freshly allocated, or the three tensors of `out` (of exactly
-    these shapes and types, contiguous, on the boxes' device), every element of which is written.  workspace: an uint8
-    tensor of at least proposals_workspace_bytes(rows) bytes, allocated when missing or too small."""
-    for t, name in ((box_preds, "box_preds"), (cls_preds, "cls_preds")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {t.dtype}")
-    dev = box_preds.device
+def _ranked_rows(box_preds, cls_preds, batch_size, pre_maxsize, post_maxsize, batch_index, dense_only=False):
+    """The rows `proposals` and `post_process` rank, in their two forms: dense, (B, N, 7 + C) and (B, N, K), or stacked, (N, 7 + C)
+    and (N, K) with `batch_index` (N).  dense_only: the call carries what only the dense form takes, so that the stacked form is
+    refused.  -> dev, B, rows per sample (0 when stacked), the kind of batch_index (0: none), batch_index as the library reads
+    it or None, 7 + C, K, the two tensors contiguous, the rows, post_maxsize"""
+    dev = _device_tensors((("box_preds", box_preds), ("cls_preds", cls_preds)))
     if cls_preds.device != dev:
         raise ValueError("box_preds and cls_preds are on different devices")
     B = int(batch_size)
@@ -1627,6 +1642,8 @@ def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int,
                 or not torch.is_tensor(batch_index) or batch_index.numel() != box_preds.shape[0]:
             raise ValueError(f"stacked form: box_preds {tuple(box_preds.shape)}, cls_preds {tuple(cls_preds.shape)} and "
                              f"batch_index must be (N, 7 + C), (N, K) and (N)")
+        if dense_only:
+            raise NotImplementedError("given labels or rois together with batch_index: no head produces that combination")
         if batch_index.device != dev:
             raise ValueError("batch_index is on another device than box_preds")
         bidx = batch_index.reshape(-1)
@@ -1642,26 +1659,27 @@ def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int,
     P = int(post_maxsize)
     if P < 0 or B < 0 or int(pre_maxsize) < 0:
         raise ValueError("batch_size, pre_maxsize and post_maxsize must not be negative")
-    want = (("rois", torch.float32, (B, P, cols)), ("roi_scores", torch.float32, (B, P)), ("roi_labels", torch.int64, (B, P)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
-    if len(out) != 3:
-        raise ValueError("out must be (rois, roi_scores, roi_labels)")
-    for t, (name, dtype, shape) in zip(out, want):
-        _dev(t, dtype, f"out {name}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
-        if t.device != dev:
-            raise ValueError(f"out {name} is on {t.device}, box_preds on {dev}")
-    rois, scores, labels = out
-    lib = load()
-    nbytes = proposals_workspace_bytes(n)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    return dev, B, per, kind, bidx, cols, K, box, cls, n, P
+
+
+def proposals(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: int, pre_maxsize: int, post_maxsize: int,
+              thresh: float, rotated: bool = True, batch_index: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_proposals on PyTorch's current stream: enqueue only, nothing is read back.
+    Dense form: box_preds (B, N, 7 + C) and cls_preds (B, N, K) float32 with B == batch_size.  Stacked form: (N1 + N2 + ..,
+    7 + C) and (N1 + N2 + .., K) with batch_index (N1 + N2 + ..), a float or integer tensor of sample numbers in any order.
+    Per sample the min(pre_maxsize, rows) highest class maxima (NaN first, equal scores by ascending row, the lowest class
+    among equal maxima) are walked by greedy NMS at `thresh` (rotated: nms_gpu, else nms_normal_gpu) up to the
+    post_maxsize-th survivor.  -> rois (B, post_maxsize, 7 + C) float32, roi_scores (B, post_maxsize) float32, roi_labels
+    (B, post_maxsize) int64 (label + 1; 1 in the padding): freshly allocated, or the three tensors of `out` (of exactly
+    these shapes and types, contiguous, on the boxes' device), every element of which is written.  workspace: an uint8
+    tensor of at least proposals_workspace_bytes(rows) bytes, allocated when missing or too small."""
+    dev, B, per, kind, bidx, cols, K, box, cls, n, P = _ranked_rows(box_preds, cls_preds, batch_size, pre_maxsize, post_maxsize, batch_index)
+    rois, scores, labels = _outputs((("rois", torch.float32, (B, P, cols), True), ("roi_scores", torch.float32, (B, P), True),
+                                     ("roi_labels", torch.int64, (B, P), True)), out, dev, anchor="box_preds")
+    workspace = _workspace(proposals_workspace_bytes(n), workspace, dev)
     with torch.cuda.device(dev):
-        check(lib.modest_proposals(n, B, per, box.data_ptr(), cols, cls.data_ptr(), K,
-                                   bidx.data_ptr() if bidx is not None else None, kind, int(pre_maxsize), P, float(thresh),
+        check(load().modest_proposals(n, B, per, box.data_ptr(), cols, cls.data_ptr(), K, _ptr(bidx), kind, int(pre_maxsize), P, float(thresh),
                                    int(bool(rotated)), rois.data_ptr(), scores.data_ptr(), labels.data_ptr(),
                                    workspace.data_ptr(), workspace.numel(), _stream()), "modest_proposals")
     return rois, scores, labels
@@ -1680,16 +1698,7 @@ def roi_targets_gt_tile() -> int:
 
 
 def roi_targets_workspace_bytes(batch_size: int, n_rois: int) -> int:
-    nb = int(load().modest_roi_targets_workspace_bytes(int(batch_size), int(n_rois)))
-    if nb < 0:
-        check(nb, "modest_roi_targets_workspace_bytes")
-    return nb
-
-
-def _cfg_get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
+    return _workspace_bytes("modest_roi_targets_workspace_bytes", batch_size, n_rois)
 
 
 def roi_target_draws(counts, cfg, np_random=None, generator=None, sample=0):
@@ -1731,9 +1740,7 @@ def roi_target_draws(counts, cfg, np_random=None, generator=None, sample=0):
 
 
 def _roi_args(rois, roi_scores, roi_labels, gt_boxes):
-    for t, name in ((rois, "rois"), (roi_scores, "roi_scores"), (roi_labels, "roi_labels"), (gt_boxes, "gt_boxes")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
+    _device_tensors((("rois", rois), ("roi_scores", roi_scores), ("roi_labels", roi_labels), ("gt_boxes", gt_boxes)), dtype_error=None)
     if rois.ndim != 3 or gt_boxes.ndim != 3 or roi_scores.shape != rois.shape[:2] or roi_labels.shape != rois.shape[:2] \
             or gt_boxes.shape[0] != rois.shape[0] or gt_boxes.shape[2] != rois.shape[2] + 1:
         raise ValueError(f"rois {tuple(rois.shape)}, roi_scores {tuple(roi_scores.shape)}, roi_labels "
@@ -1853,9 +1860,7 @@ def roi_targets(rois: torch.Tensor, roi_scores: torch.Tensor, roi_labels: torch.
     s32 = roi_scores.float().contiguous()
     lab = roi_labels.long().contiguous()
     gt = gt_boxes if gt_boxes.dtype == torch.float32 else gt_boxes.float()
-    need = roi_targets_workspace_bytes(B, N)
-    if workspace is None or workspace.numel() < need or workspace.device != dev:
-        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+    workspace = _workspace(roi_targets_workspace_bytes(B, N), workspace, dev)
     if counts_pinned is None or counts_pinned.numel() < 3 * B:
         counts_pinned = torch.zeros((max(3 * B, 16),), dtype=torch.int32).pin_memory()
     if picks_pinned is not None and picks_pinned.numel() < 2 * B * M:
@@ -1899,10 +1904,7 @@ def post_process_tile() -> int:
 
 
 def post_process_workspace_bytes(n_rows: int, batch_size: int) -> int:
-    nb = int(load().modest_post_process_workspace_bytes(int(n_rows), int(batch_size)))
-    if nb < 0:
-        check(nb, "modest_post_process_workspace_bytes")
-    return nb
+    return _workspace_bytes("modest_post_process_workspace_bytes", n_rows, batch_size)
 
 
 def post_process_table_words(batch_size: int, n_thresh: int) -> int:
@@ -1930,42 +1932,8 @@ def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: i
     workspace: uint8 device tensor of post_process_workspace_bytes(rows, B); table: pinned int32 tensor of
     post_process_table_words(B, len(recall_thresh)); both allocated when missing or too small.  A table serves one stream
     at a time: the kernels write it, and it is read here once the stream has been synchronised."""
-    for t, name in ((box_preds, "box_preds"), (cls_preds, "cls_preds")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {t.dtype}")
-    dev = box_preds.device
-    if cls_preds.device != dev:
-        raise ValueError("box_preds and cls_preds are on different devices")
-    B = int(batch_size)
-    if batch_index is None:
-        if box_preds.ndim != 3 or cls_preds.ndim != 3 or box_preds.shape[:2] != cls_preds.shape[:2] or box_preds.shape[0] != B:
-            raise ValueError(f"dense form: box_preds {tuple(box_preds.shape)} and cls_preds {tuple(cls_preds.shape)} must be "
-                             f"(batch_size = {B}, N, 7 + C) and (batch_size, N, K)")
-        per, kind, bidx = int(box_preds.shape[1]), 0, None
-    else:
-        if box_preds.ndim != 2 or cls_preds.ndim != 2 or box_preds.shape[0] != cls_preds.shape[0] \
-                or not torch.is_tensor(batch_index) or batch_index.numel() != box_preds.shape[0]:
-            raise ValueError(f"stacked form: box_preds {tuple(box_preds.shape)}, cls_preds {tuple(cls_preds.shape)} and "
-                             f"batch_index must be (N, 7 + C), (N, K) and (N)")
-        if labels is not None or rois is not None:
-            raise NotImplementedError("given labels or rois together with batch_index: no head produces that combination")
-        if batch_index.device != dev:
-            raise ValueError("batch_index is on another device than box_preds")
-        bidx = batch_index.reshape(-1)
-        if bidx.dtype not in _BATCH_INDEX_KINDS:
-            bidx = bidx.float() if bidx.dtype.is_floating_point else bidx.long()
-        bidx = bidx.contiguous()
-        per, kind = 0, _BATCH_INDEX_KINDS[bidx.dtype]
-    cols, K = int(box_preds.shape[-1]), int(cls_preds.shape[-1])
-    if cols < 7 or K < 1:
-        raise ValueError(f"box_preds needs 7 + C columns and cls_preds K >= 1, got {cols} and {K}")
-    box, cls = box_preds.contiguous(), cls_preds.contiguous()
-    n = int(box.numel() // cols)
-    P = int(post_maxsize)
-    if P < 0 or B < 0 or int(pre_maxsize) < 0:
-        raise ValueError("batch_size, pre_maxsize and post_maxsize must not be negative")
+    dev, B, per, kind, bidx, cols, K, box, cls, n, P = _ranked_rows(box_preds, cls_preds, batch_size, pre_maxsize, post_maxsize, batch_index,
+                                                                    dense_only=labels is not None or rois is not None)
     if labels is not None:
         if not torch.is_tensor(labels) or labels.device != dev or labels.numel() != n:
             raise ValueError(f"labels must be a device tensor of (batch_size, N) = ({B}, {per}) elements")
@@ -1992,36 +1960,22 @@ def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: i
                 raise ValueError(f"rois {tuple(rois.shape)} must be (batch_size = {B}, R, 7 + C)")
             rois = rois.contiguous()
             R, rcols = int(rois.shape[1]), int(rois.shape[2])
-    want = (("pred_boxes", torch.float32, (B, P, cols)), ("pred_scores", torch.float32, (B, P)), ("pred_labels", torch.int64, (B, P)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in want)
-    if len(out) != 3:
-        raise ValueError("out must be (pred_boxes, pred_scores, pred_labels)")
-    for t, (name, dtype, shape) in zip(out, want):
-        _dev(t, dtype, f"out {name}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"out {name} has shape {tuple(t.shape)}, expected {shape}")
-        if t.device != dev:
-            raise ValueError(f"out {name} is on {t.device}, box_preds on {dev}")
-    boxes, scores, labs = out
-    lib = load()
-    nbytes = post_process_workspace_bytes(n, B)
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    _dev(workspace, torch.uint8, "workspace")
+    boxes, scores, labs = _outputs((("pred_boxes", torch.float32, (B, P, cols), True), ("pred_scores", torch.float32, (B, P), True),
+                                    ("pred_labels", torch.int64, (B, P), True)), out, dev, anchor="box_preds")
+    workspace = _workspace(post_process_workspace_bytes(n, B), workspace, dev)
     stride = 2 + 2 * T
     words = post_process_table_words(B, T)
     if table is None or table.numel() < words:
         table = torch.zeros((max(words, 16),), dtype=torch.int32).pin_memory()
     if not table.is_pinned() or table.dtype != torch.int32 or not table.is_contiguous():
         raise ValueError("table must be a contiguous pinned int32 tensor")
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None      # noqa: E731
+    ptr = _ptr_filled
     gs = tuple(int(s) for s in gt.stride()) if gt is not None else (0, 0, 0)
     with torch.cuda.device(dev):
-        check(lib.modest_post_process(n, B, per, ptr(box), cols, ptr(cls), K, bidx.data_ptr() if bidx is not None else None, kind,
+        check(load().modest_post_process(n, B, per, ptr(box), cols, ptr(cls), K, _ptr(bidx), kind,
                                       int(bool(normalized)), int(score_thresh is not None),
                                       float(score_thresh) if score_thresh is not None else 0.0, int(bool(output_raw_score)),
-                                      labels.data_ptr() if labels is not None else None, int(pre_maxsize), P, float(nms_thresh),
+                                      _ptr(labels), int(pre_maxsize), P, float(nms_thresh),
                                       int(bool(rotated)), int(gt is not None), G, ptr(gt), *gs, R, ptr(rois), rcols, T,
                                       _np_ptr(thr) if T else None, ptr(boxes), ptr(scores), ptr(labs), table.data_ptr(),
                                       workspace.data_ptr(), workspace.numel(), _stream()), "modest_post_process")
@@ -2035,34 +1989,10 @@ def post_process(box_preds: torch.Tensor, cls_preds: torch.Tensor, batch_size: i
 
 
 # --------------------------------------------------------------------------- what the three head losses share
-def _loss_workspace_bytes(fn_name: str, *args) -> int:
-    nb = int(getattr(load(), fn_name)(*(int(a) for a in args)))
-    if nb < 0:
-        check(nb, fn_name)
-    return nb
-
-
 def _loss_out(want, out, dev):
-    """`want`: (name, shape, needed) per buffer -> the float32 buffers on `dev`, None where none is needed: new ones, or those
-    of `out` once they are found to be just these"""
-    if out is None:
-        return [torch.empty(shape, dtype=torch.float32, device=dev) if need else None for _, shape, need in want]
-    if len(out) != len(want):
-        raise ValueError(f"out must be ({', '.join(name for name, _, _ in want)})")
-    for t, (name, shape, need) in zip(out, want):
-        if (t is not None) != need:
-            raise ValueError(f"out {name} must be {'a tensor' if need else 'None'}")
-        if t is not None:
-            _dev(t, torch.float32, f"out {name}")
-            if tuple(t.shape) != shape or t.device != dev:
-                raise ValueError(f"out {name} has shape {tuple(t.shape)} on {t.device}, expected {shape} on {dev}")
-    return out
-
-
-def _loss_workspace(nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
-    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
-        workspace = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
-    return _dev(workspace, torch.uint8, "workspace")
+    """`want`: (name, shape, needed) per buffer -> the float32 buffers on `dev`, None where none is needed (`_outputs`)"""
+    return _outputs([(name, torch.float32, shape, bool(need)) for name, shape, need in want], out, dev,
+                    absent=("must be None", "must be a tensor"))
 
 
 def _loss_backward(fn_name: str, names, grads, upstream: torch.Tensor):
@@ -2092,7 +2022,7 @@ ANCHOR_LOSS_MAX_BATCH = 65535   # samples per call: the grid's second dimension
 
 
 def anchor_loss_workspace_bytes(batch_size: int, n_anchors: int) -> int:
-    return _loss_workspace_bytes("modest_anchor_loss_workspace_bytes", batch_size, n_anchors)
+    return _workspace_bytes("modest_anchor_loss_workspace_bytes", batch_size, n_anchors)
 
 
 def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Optional[torch.Tensor], labels: torch.Tensor,
@@ -2107,18 +2037,9 @@ def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Opt
     -> (losses (4) float32 [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss], grads): grads is None without want_grad, else
     (grad_cls, grad_box, grad_dir or None) of the predictions' shapes, d rpn_loss / d prediction, every element written.
     `out` = (losses, grad_cls, grad_box, grad_dir) supplies the buffers (the gradients None without want_grad)."""
-    for t, name in ((cls_preds, "cls_preds"), (box_preds, "box_preds"), (dir_preds, "dir_preds"), (labels, "labels"),
-                    (reg_targets, "reg_targets"), (anchors, "anchors"), (code_weights, "code_weights")):
-        if t is None and name == "dir_preds":
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if name == "labels":
-            if t.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"labels must be int32 or int64, got {t.dtype}")
-        elif t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-    dev = cls_preds.device
+    dev = _device_tensors((("cls_preds", cls_preds), ("box_preds", box_preds), ("dir_preds", dir_preds), ("labels", labels),
+                           ("reg_targets", reg_targets), ("anchors", anchors), ("code_weights", code_weights)),
+                          dtypes={"labels": (torch.int32, torch.int64)}, optional=("dir_preds",), dtype_error=TypeError)
     if cls_preds.ndim != 3 or box_preds.ndim != 3 or cls_preds.shape[:2] != box_preds.shape[:2]:
         raise ValueError(f"cls_preds {tuple(cls_preds.shape)} and box_preds {tuple(box_preds.shape)} must be (B, N, C) and (B, N, code)")
     B, N, K = (int(v) for v in cls_preds.shape)
@@ -2153,8 +2074,8 @@ def anchor_loss(cls_preds: torch.Tensor, box_preds: torch.Tensor, dir_preds: Opt
     dirp = dir_preds.contiguous() if dir_preds is not None else None
     losses, gcls, gbox, gdir = _loss_out((("losses", (4,), True), ("grad_cls", (B, N, K), want_grad), ("grad_box", (B, N, code), want_grad),
                                           ("grad_dir", (B, N, bins), want_grad and dirp is not None)), out, dev)
-    workspace = _loss_workspace(anchor_loss_workspace_bytes(B, N), workspace, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    workspace = _workspace(anchor_loss_workspace_bytes(B, N), workspace, dev)
+    ptr = _ptr
     with torch.cuda.device(dev):
         check(load().modest_anchor_loss(B, N, K, code, bins, ptr(cls), ptr(box), ptr(dirp), ptr(labels),
                                         int(labels.dtype == torch.int64), ptr(reg_targets), ptr(anchors), int(anchors.shape[1]),
@@ -2179,7 +2100,7 @@ _ROI_LOSS_LABELS = {torch.int32: 0, torch.int64: 1, torch.float32: 2}
 
 
 def roi_loss_workspace_bytes(n_rows: int) -> int:
-    return _loss_workspace_bytes("modest_roi_loss_workspace_bytes", n_rows)
+    return _workspace_bytes("modest_roi_loss_workspace_bytes", n_rows)
 
 
 def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: torch.Tensor, reg_valid_mask: torch.Tensor,
@@ -2197,18 +2118,8 @@ def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: to
     `out` = (table, grad_cls, grad_reg) supplies the buffers (the gradients None without want_grad)."""
     named = (("rcnn_cls", rcnn_cls), ("rcnn_reg", rcnn_reg), ("rcnn_cls_labels", rcnn_cls_labels), ("reg_valid_mask", reg_valid_mask),
              ("gt_of_rois", gt_of_rois), ("gt_of_rois_src", gt_of_rois_src), ("rois", rois), ("code_weights", code_weights))
-    for name, t in named:
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if name == "rcnn_cls_labels":
-            if t.dtype not in _ROI_LOSS_LABELS:
-                raise TypeError(f"rcnn_cls_labels must be int32, int64 or float32, got {t.dtype}")
-        elif name == "reg_valid_mask":
-            if t.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"reg_valid_mask must be int32 or int64, got {t.dtype}")
-        elif t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-    dev = rcnn_cls.device
+    dev = _device_tensors(named, dtypes={"rcnn_cls_labels": tuple(_ROI_LOSS_LABELS), "reg_valid_mask": (torch.int32, torch.int64)},
+                          dtype_error=TypeError)
     if rcnn_reg.ndim != 2:
         raise ValueError(f"rcnn_reg {tuple(rcnn_reg.shape)} must be (R, code)")
     R, code = (int(v) for v in rcnn_reg.shape)
@@ -2235,8 +2146,8 @@ def roi_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, rcnn_cls_labels: to
             raise ValueError(f"{name} is on {t.device}, rcnn_cls on {dev}")
     cls, reg = rcnn_cls.reshape(-1).contiguous(), rcnn_reg.contiguous()
     table, gcls, greg = _loss_out((("table", (6,), True), ("grad_cls", (R,), want_grad), ("grad_reg", (R, code), want_grad)), out, dev)
-    workspace = _loss_workspace(roi_loss_workspace_bytes(R), workspace, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    workspace = _workspace(roi_loss_workspace_bytes(R), workspace, dev)
+    ptr = _ptr
     stride = lambda t: int(t.stride(0)) if R > 1 else int(t.shape[1])      # noqa: E731
     with torch.cuda.device(dev):
         check(load().modest_roi_loss(R, code, ptr(cls), ptr(reg), ptr(rcnn_cls_labels), _ROI_LOSS_LABELS[rcnn_cls_labels.dtype],
@@ -2263,7 +2174,7 @@ POINT_LOSS_TABLE = ("point_loss_cls", "point_loss_part", "point_loss_box", "poin
 
 
 def point_loss_workspace_bytes(n_rows: int) -> int:
-    return _loss_workspace_bytes("modest_point_loss_workspace_bytes", n_rows)
+    return _workspace_bytes("modest_point_loss_workspace_bytes", n_rows)
 
 
 def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Optional[torch.Tensor] = None,
@@ -2287,17 +2198,8 @@ def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Option
         raise ValueError("box_preds, box_labels and code_weights come together")
     named = (("cls_preds", cls_preds), ("labels", labels), ("part_preds", part_preds), ("part_labels", part_labels),
              ("box_preds", box_preds), ("box_labels", box_labels), ("code_weights", code_weights))
-    for name, t in named:
-        if t is None and name not in ("cls_preds", "labels"):
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if name == "labels":
-            if t.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"labels must be int32 or int64, got {t.dtype}")
-        elif t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-    dev = cls_preds.device
+    dev = _device_tensors(named, dtypes={"labels": (torch.int32, torch.int64)}, optional=[name for name, _ in named[2:]],
+                          dtype_error=TypeError)
     if cls_preds.ndim < 2:
         raise ValueError(f"cls_preds {tuple(cls_preds.shape)} must be (N, num_class) or (B, n, num_class)")
     K = int(cls_preds.shape[-1])
@@ -2334,8 +2236,8 @@ def point_loss(cls_preds: torch.Tensor, labels: torch.Tensor, part_preds: Option
     table, gcls, gpart, gbox = _loss_out((("table", (5,), True), ("grad_cls", (N, K), want_grad),
                                           ("grad_part", (N, POINT_LOSS_PART), want_grad and with_part),
                                           ("grad_box", (N, code), want_grad and with_box)), out, dev)
-    workspace = _loss_workspace(point_loss_workspace_bytes(N), workspace, dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    workspace = _workspace(point_loss_workspace_bytes(N), workspace, dev)
+    ptr = _ptr
     with torch.cuda.device(dev):
         check(load().modest_point_loss(N, K, code, ptr(cls), ptr(labels), int(labels.dtype == torch.int64), ptr(part), ptr(part_t),
                                        ptr(box), ptr(box_t), ptr(code_weights), float(beta), float(cls_weight), float(part_weight),
@@ -2357,21 +2259,7 @@ BOX_DECODE_MAX_BINS = 8               # direction bins
 BOX_DECODE_MAX_CLASS = 32             # class columns of a point
 
 
-def _decode_tensors(named, dev=None):
-    for name, t in named:
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{name} must be a device tensor (PyTorch-ROCm 'cuda')")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        dev = t.device if dev is None else dev
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, {named[0][0]} on {dev}")
-    return dev
-
-
-def _decode_out(out, shape, dev):
+def _decode_out(out, shape, dev):      # one buffer, refused in one message of its own: not a call of _outputs
     if out is None:
         return torch.empty(shape, dtype=torch.float32, device=dev)
     if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or out.device != dev
@@ -2397,7 +2285,8 @@ def anchor_decode(box_preds: torch.Tensor, anchors: torch.Tensor, dir_cls_preds:
     contiguous float32 device tensors; the anchors are read once per row for every sample.  The scalars are rounded to float32,
     as torch rounds a Python scalar that meets a float32 tensor.
     -> boxes (B, N, 7 + C) float32 (`out` supplies it), every element written"""
-    dev = _decode_tensors((("box_preds", box_preds), ("anchors", anchors), ("dir_cls_preds", dir_cls_preds)))
+    dev = _device_tensors((("box_preds", box_preds), ("anchors", anchors), ("dir_cls_preds", dir_cls_preds)),
+                          optional=("dir_cls_preds",), dtype_error=TypeError, same_device=True)
     if box_preds.ndim != 3 or anchors.ndim != 2:
         raise ValueError(f"box_preds {tuple(box_preds.shape)} must be (B, N, code) and anchors {tuple(anchors.shape)} (N, 7 + C)")
     B, N, code = (int(v) for v in box_preds.shape)
@@ -2418,7 +2307,7 @@ def anchor_decode(box_preds: torch.Tensor, anchors: torch.Tensor, dir_cls_preds:
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
     boxes = _decode_out(out, (B, N, cols), dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    ptr = _ptr
     with torch.cuda.device(dev):
         check(load().modest_anchor_decode(B, N, code, int(bool(sincos)), ptr(box_preds), ptr(anchors), ptr(dir_cls_preds), bins,
                                           float(dir_offset), float(dir_limit_offset), ptr(boxes), _stream()), "modest_anchor_decode")
@@ -2432,8 +2321,8 @@ def point_decode(point_box_preds: torch.Tensor, points: torch.Tensor, point_cls_
     of at least 3 (the view point_coords[:, 1:4] is read in place); mean_size (K, 3) contiguous, or None for use_mean_size =
     False: float32 device tensors.
     -> boxes (N, 7 + C) float32 (`out` supplies it), every element written"""
-    dev = _decode_tensors((("point_box_preds", point_box_preds), ("points", points), ("point_cls_preds", point_cls_preds),
-                           ("mean_size", mean_size)))
+    dev = _device_tensors((("point_box_preds", point_box_preds), ("points", points), ("point_cls_preds", point_cls_preds),
+                           ("mean_size", mean_size)), optional=("mean_size",), dtype_error=TypeError, same_device=True)
     if point_box_preds.ndim != 2 or point_cls_preds.ndim != 2 or points.ndim != 2:
         raise ValueError(f"point_box_preds {tuple(point_box_preds.shape)}, point_cls_preds {tuple(point_cls_preds.shape)} and "
                          f"points {tuple(points.shape)} must be (N, 8 + C), (N, K) and (N, 3)")
@@ -2468,7 +2357,7 @@ def roi_decode(rois: torch.Tensor, box_preds: torch.Tensor, *, out=None) -> torc
     rois (R, code) or (B, M, code) and box_preds (R, code) or (B, M, code), contiguous float32 device tensors with the same
     number of rows; neither is written.
     -> boxes (R, code) float32 (`out` supplies it), every element written"""
-    dev = _decode_tensors((("rois", rois), ("box_preds", box_preds)))
+    dev = _device_tensors((("rois", rois), ("box_preds", box_preds)), dtype_error=TypeError, same_device=True)
     if rois.ndim < 2 or box_preds.ndim < 2:
         raise ValueError(f"rois {tuple(rois.shape)} and box_preds {tuple(box_preds.shape)} must be (R, code) or (B, M, code)")
     code = int(box_preds.shape[-1])

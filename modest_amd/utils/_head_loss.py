@@ -1,15 +1,32 @@
 """What the ``get_loss`` drop-ins of the anchor, RoI and point heads share (``anchor_head_loss``, ``roi_head_loss``,
 ``point_head_loss``; DESIGN.md sections 7p - 7r): the config lookup, the hand-back of a head that overrides a part of the loss
 to the method ``bind`` replaced, the buffers kept on the head, the code weights, the autograd function around the fused
-forward + gradient call, and the one host wait."""
+forward + gradient call, and the one host wait.  The config lookup and the two grow-only buffers (``device_workspace``,
+``pinned_table``) also serve the other drop-ins that keep buffers on a head or a detector (``proposal_layer``, ``roi_targets``,
+``post_processing``)."""
 import torch
 from torch.autograd.function import once_differentiable
 
 
-def _get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
+from ..ops import _cfg_get as _get      # noqa: F401  the config lookup of every drop-in: cfg[name] or cfg.name, with a default
+
+
+def device_workspace(owner, attr, nbytes, dev):
+    """the uint8 device workspace kept on `owner` as `attr`: replaced when it is too small or on another device, never shrunk"""
+    ws = getattr(owner, attr, None)
+    if ws is None or ws.numel() < nbytes or ws.device != dev:
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        setattr(owner, attr, ws)
+    return ws
+
+
+def pinned_table(owner, attr, words):
+    """the pinned int32 table kept on `owner` as `attr`: replaced when it is too small, never shrunk"""
+    table = getattr(owner, attr, None)
+    if table is None or table.numel() < words:
+        table = torch.zeros((max(words, 16),), dtype=torch.int32).pin_memory()
+        setattr(owner, attr, table)
+    return table
 
 
 def replaced_get_loss(head_type, original, parts):
@@ -28,10 +45,7 @@ def replaced_get_loss(head_type, original, parts):
 def buffers(head, prefix, workspace_bytes, table_len, dev):
     """the workspace and the pinned table kept on `head` as `prefix`_workspace and `prefix`_table; a table serves one stream
     at a time"""
-    ws = getattr(head, prefix + "_workspace", None)
-    if ws is None or ws.numel() < workspace_bytes or ws.device != dev:
-        ws = torch.empty((max(workspace_bytes, 256),), dtype=torch.uint8, device=dev)
-        setattr(head, prefix + "_workspace", ws)
+    ws = device_workspace(head, prefix + "_workspace", workspace_bytes, dev)
     table = getattr(head, prefix + "_table", None)
     if table is None:
         table = torch.zeros((table_len,), dtype=torch.float32).pin_memory()

@@ -133,26 +133,15 @@ class StandIn(types.ModuleType):
         return missing
 
 
-def _bind_sparse_conv():
-    """spconv := modest_amd.utils.spconv unless a real spconv is imported or installed -> the module bound, or None"""
-    ours = importlib.import_module(SPCONV)
+def _bind_spconv(ours_name, replaceable=()):
+    """spconv := the module `ours_name` (SPCONV or SPCONV_INVERSE) unless a real spconv is imported or installed; a stand-in
+    and those of our own modules named in `replaceable` give way -> the module bound, or None"""
+    ours = importlib.import_module(ours_name)
     mod = sys.modules.get("spconv")
     if mod is None and importlib.util.find_spec("spconv") is not None:
         return None   # the real package is installed: leave it alone
-    if mod is not None and mod is not ours and not isinstance(mod, StandIn):
-        return None   # ... or already imported
-    sys.modules["spconv"] = ours
-    sys.modules["spconv.utils"] = ours.utils
-    return ours
-
-
-def _bind_sparse_inverse():
-    """spconv := modest_amd.utils.spconv_inverse unless a real spconv is imported or installed -> the module bound, or None"""
-    ours = importlib.import_module(SPCONV_INVERSE)
-    mod = sys.modules.get("spconv")
-    if mod is None and importlib.util.find_spec("spconv") is not None:
-        return None   # the real package is installed: leave it alone
-    if mod is not None and mod is not ours and mod is not importlib.import_module(SPCONV) and not isinstance(mod, StandIn):
+    if mod is not None and mod is not ours and not isinstance(mod, StandIn) \
+            and not any(mod is importlib.import_module(name) for name in replaceable):
         return None   # ... or already imported
     sys.modules["spconv"] = ours
     sys.modules["spconv.utils"] = ours.utils
@@ -190,36 +179,45 @@ def _bind_roiaware_pool(before):
     return ours
 
 
+def _bind_onto(module_name, class_name, ours_name, *bind_args):
+    """the class `class_name` of the reference's module `module_name`, which is imported for it if it is not yet, handed to
+    ``bind`` of our module `ours_name` -> the reference's module, or None where it cannot be imported (no pcdet on the path, or
+    one that does not import here: nothing to bind onto) or lacks the class"""
+    mod = sys.modules.get(module_name)
+    if mod is None:
+        try:
+            mod = importlib.import_module(module_name)
+        except ImportError:
+            return None
+    cls = getattr(mod, class_name, None)
+    if cls is None:
+        return None
+    importlib.import_module(ours_name).bind(cls, *bind_args)
+    return mod
+
+
+def _bind_onto_each(names, ours_name, with_class_name=False):
+    """`_bind_onto` for every module -> class of `names` (`bind` is told the class name too with `with_class_name`)
+    -> {module name: module} of the modules bound, or None where none of the modules can be imported"""
+    bound, found = {}, False
+    for name, cls_name in names.items():
+        mod = _bind_onto(name, cls_name, ours_name, *((cls_name,) if with_class_name else ()))
+        found = found or sys.modules.get(name) is not None      # imported before or just now, with or without its class
+        if mod is not None:
+            bound[name] = mod
+    return bound if found else None
+
+
 def _bind_point_targets():
     """PointHeadTemplate.assign_stack_targets := ours, in the reference's module if it is imported or can be
     -> that module, or None"""
-    mod = sys.modules.get(POINT_TARGETS_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(POINT_TARGETS_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    head = getattr(mod, "PointHeadTemplate", None)
-    if head is None:
-        return None
-    importlib.import_module(POINT_TARGETS).bind(head)
-    return mod
+    return _bind_onto(POINT_TARGETS_NAME, "PointHeadTemplate", POINT_TARGETS)
 
 
 def _bind_proposal_layer():
     """RoIHeadTemplate.proposal_layer := ours, in the reference's module if it is imported or can be
     -> that module, or None"""
-    mod = sys.modules.get(PROPOSAL_LAYER_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(PROPOSAL_LAYER_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    head = getattr(mod, "RoIHeadTemplate", None)
-    if head is None:
-        return None
-    importlib.import_module(PROPOSAL_LAYER).bind(head)
-    return mod
+    return _bind_onto(PROPOSAL_LAYER_NAME, "RoIHeadTemplate", PROPOSAL_LAYER)
 
 
 def bind_roi_targets():
@@ -227,17 +225,7 @@ def bind_roi_targets():
     two-stage heads -- in the reference's module if it is imported or can be -> that module, or
     None.  A function of its own: install() and what it returns stay as they are.  Idempotent; before or after
     ``import pcdet.models``; touches no GPU state."""
-    mod = sys.modules.get(ROI_TARGETS_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(ROI_TARGETS_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    head = getattr(mod, "RoIHeadTemplate", None)
-    if head is None:
-        return None
-    importlib.import_module(ROI_TARGETS).bind(head)
-    return mod
+    return _bind_onto(ROI_TARGETS_NAME, "RoIHeadTemplate", ROI_TARGETS)
 
 
 def bind_post_processing():
@@ -246,17 +234,7 @@ def bind_post_processing():
     module, or None.  A function of its own: install() and what it returns stay as they are.  Only the template's own
     method is set, so a subclass that overrides it (SECONDNetIoU) keeps its own.  Idempotent; before or after
     ``import pcdet.models``; touches no GPU state."""
-    mod = sys.modules.get(POST_PROCESSING_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(POST_PROCESSING_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    detector = getattr(mod, "Detector3DTemplate", None)
-    if detector is None:
-        return None
-    importlib.import_module(POST_PROCESSING).bind(detector)
-    return mod
+    return _bind_onto(POST_PROCESSING_NAME, "Detector3DTemplate", POST_PROCESSING)
 
 
 def bind_anchor_loss():
@@ -265,17 +243,7 @@ def bind_anchor_loss():
     function of its own: install() and what it returns stay as they are.  Only the template's own method is set, and the
     one it had is kept: a head that overrides get_cls_layer_loss or get_box_reg_layer_loss (AnchorHeadMulti) is handed to
     it.  Idempotent; before or after ``import pcdet.models``; touches no GPU state."""
-    mod = sys.modules.get(ANCHOR_LOSS_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(ANCHOR_LOSS_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    head = getattr(mod, "AnchorHeadTemplate", None)
-    if head is None:
-        return None
-    importlib.import_module(ANCHOR_LOSS).bind(head)
-    return mod
+    return _bind_onto(ANCHOR_LOSS_NAME, "AnchorHeadTemplate", ANCHOR_LOSS)
 
 
 def bind_roi_loss():
@@ -285,17 +253,7 @@ def bind_roi_loss():
     kept: a head that overrides get_box_reg_layer_loss or get_box_cls_layer_loss is handed to it, and a head class with a
     get_loss of its own (SECONDHead) keeps that.  Idempotent; before or after ``import pcdet.models``; touches no GPU
     state."""
-    mod = sys.modules.get(ROI_LOSS_NAME)
-    if mod is None:
-        try:
-            mod = importlib.import_module(ROI_LOSS_NAME)
-        except ImportError:
-            return None   # no pcdet on the path (or one that does not import here): nothing to bind onto
-    head = getattr(mod, "RoIHeadTemplate", None)
-    if head is None:
-        return None
-    importlib.import_module(ROI_LOSS).bind(head)
-    return mod
+    return _bind_onto(ROI_LOSS_NAME, "RoIHeadTemplate", ROI_LOSS)
 
 
 def bind_point_loss():
@@ -306,21 +264,7 @@ def bind_point_loss():
     not their template; the method each had is kept: a head that overrides get_cls_layer_loss, get_part_layer_loss or
     get_box_layer_loss is handed to it.  A module that lacks its class is skipped.  Idempotent; before or after
     ``import pcdet.models``; touches no GPU state."""
-    bound, found = {}, False
-    for name, cls_name in POINT_LOSS_NAMES.items():
-        mod = sys.modules.get(name)
-        if mod is None:
-            try:
-                mod = importlib.import_module(name)
-            except ImportError:
-                continue      # no pcdet on the path (or one that does not import here): nothing to bind onto
-        found = True
-        head = getattr(mod, cls_name, None)
-        if head is None:
-            continue
-        importlib.import_module(POINT_LOSS).bind(head)
-        bound[name] = mod
-    return bound if found else None
+    return _bind_onto_each(POINT_LOSS_NAMES, POINT_LOSS)
 
 
 def bind_box_decode():
@@ -330,21 +274,7 @@ def bind_box_decode():
     of its own: install() and what it returns stay as they are.  Only the templates' own methods are set, so a head that
     overrides generate_predicted_boxes keeps its own.  A module that lacks its class is skipped.  Idempotent; before or after
     ``import pcdet.models``; touches no GPU state."""
-    bound, found = {}, False
-    for name, cls_name in BOX_DECODE_NAMES.items():
-        mod = sys.modules.get(name)
-        if mod is None:
-            try:
-                mod = importlib.import_module(name)
-            except ImportError:
-                continue      # no pcdet on the path (or one that does not import here): nothing to bind onto
-        found = True
-        head = getattr(mod, cls_name, None)
-        if head is None:
-            continue
-        importlib.import_module(BOX_DECODE).bind(head, cls_name)
-        bound[name] = mod
-    return bound if found else None
+    return _bind_onto_each(BOX_DECODE_NAMES, BOX_DECODE, with_class_name=True)
 
 
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
@@ -365,11 +295,11 @@ def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets
         if ours is not None and not stand_ins:
             bound[POINT_STACK_NAME] = ours
     if sparse_conv:
-        ours = _bind_sparse_conv()
+        ours = _bind_spconv(SPCONV)
         if ours is not None and not stand_ins:
             bound["spconv"] = ours
     if sparse_inverse:
-        ours = _bind_sparse_inverse()
+        ours = _bind_spconv(SPCONV_INVERSE, replaceable=(SPCONV,))
         if ours is not None and not stand_ins:
             bound["spconv"] = ours
     if stand_ins:

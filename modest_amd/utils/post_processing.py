@@ -20,31 +20,20 @@ detector class; ``pcdet_bind.bind_post_processing()`` does that for the referenc
 """
 import torch
 
+from ._head_loss import _get, device_workspace, pinned_table
+
 POST_MAX = 1024       # survivors per sample: the kept list is held in LDS (csrc/prop_walk.h)
 BATCH_MAX = 65535     # samples per call: 16 sample bits of the sort key
 THRESH_MAX = 16       # len(RECALL_THRESH_LIST): the thresholds travel in a kernel's arguments
 NMS_TYPES = {"nms_gpu": True, "nms_normal_gpu": False}   # name -> rotated
 
 
-def _get(cfg, name, *default):
-    if isinstance(cfg, dict):
-        return cfg.get(name, *default) if default else cfg[name]
-    return getattr(cfg, name, *default)
-
-
 def _buffers(detector, dev, rows, B, T):
     """the workspace and the pinned table kept on `detector`: they grow with the largest call.  Every call ends in a
     stream synchronise, so no kernel of an earlier call can still write a table that is replaced here."""
     from .. import ops
-    need = ops.post_process_workspace_bytes(rows, B)
-    ws = getattr(detector, "_modest_post_process_workspace", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = detector._modest_post_process_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    words = ops.post_process_table_words(B, T)
-    table = getattr(detector, "_modest_post_process_table", None)
-    if table is None or table.numel() < words:
-        table = detector._modest_post_process_table = torch.zeros((max(words, 16),), dtype=torch.int32).pin_memory()
-    return ws, table
+    return (device_workspace(detector, "_modest_post_process_workspace", ops.post_process_workspace_bytes(rows, B), dev),
+            pinned_table(detector, "_modest_post_process_table", ops.post_process_table_words(B, T)))
 
 
 @torch.no_grad()

@@ -14,13 +14,11 @@ row, equal class maxima to the lowest class, and a NaN score ranks above every n
 """
 import torch
 
-POST_MAX = 1024       # survivors per sample: the kept list is held in LDS (csrc/proposals.hip)
+from ._head_loss import _get, device_workspace
+
+POST_MAX = 1024       # survivors per sample: the kept list is held in LDS (csrc/prop_walk.h)
 BATCH_MAX = 65535     # samples per call: 16 sample bits of the sort key
 NMS_TYPES = {"nms_gpu": True, "nms_normal_gpu": False}   # name -> rotated
-
-
-def _get(cfg, name):
-    return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
 
 
 @torch.no_grad()
@@ -64,10 +62,7 @@ def proposal_layer(self, batch_dict, nms_config):
     box = box_preds if box_preds.dtype == torch.float32 else box_preds.float()
     cls = cls_preds if cls_preds.dtype == torch.float32 else cls_preds.float()
     try:
-        need = ops.proposals_workspace_bytes(box.numel() // box.shape[-1])
-        ws = getattr(self, '_modest_proposals_workspace', None)
-        if ws is None or ws.numel() < need or ws.device != box.device:
-            ws = self._modest_proposals_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=box.device)
+        ws = device_workspace(self, '_modest_proposals_workspace', ops.proposals_workspace_bytes(box.numel() // box.shape[-1]), box.device)
         rois, roi_scores, roi_labels = ops.proposals(box, cls, batch_size, pre, post, float(_get(nms_config, "NMS_THRESH")),
                                                      rotated=NMS_TYPES[nms_type], batch_index=batch_index, workspace=ws)
     except ModestHipError as e:

@@ -18,6 +18,8 @@ that for the reference's ``RoIHeadTemplate``.  ``forward`` has ``ProposalTargetL
 """
 import torch
 
+from ._head_loss import device_workspace, pinned_table
+
 BATCH_MAX = 65535     # samples per call
 COLS_MAX = 4096       # 7 + C
 KEYS = ("rois", "gt_of_rois", "gt_iou_of_rois", "roi_scores", "roi_labels", "reg_valid_mask", "rcnn_cls_labels",
@@ -37,24 +39,17 @@ def _config(head):
 def _buffers(head, dev, B, N, M):
     """the workspace and the two pinned tables kept on `head`: they grow with the largest call"""
     from .. import ops
-    need = ops.roi_targets_workspace_bytes(B, N)
-    ws = getattr(head, "_modest_roi_targets_workspace", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = head._modest_roi_targets_workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    counts = getattr(head, "_modest_roi_targets_counts", None)
-    if counts is None or counts.numel() < 3 * B:
-        counts = head._modest_roi_targets_counts = torch.zeros((max(3 * B, 16),), dtype=torch.int32).pin_memory()
+    ws = device_workspace(head, "_modest_roi_targets_workspace", ops.roi_targets_workspace_bytes(B, N), dev)
+    counts = pinned_table(head, "_modest_roi_targets_counts", 3 * B)
     picks = getattr(head, "_modest_roi_targets_picks", None)
-    if picks is None or picks.numel() < 2 * B * M:
+    if picks is not None and picks.numel() < 2 * B * M:
         # The sample kernel reads this table where it lies, through a pointer PyTorch's host allocator does not see.  The
         # host writes it in every call only after that call's match has synchronised the stream, so the sample kernel of
         # the call before has read it.  A table that is replaced goes back to the allocator at once, though, and could be
         # handed out and overwritten while that kernel still waits: so the stream is synchronised before it is dropped (on
         # growth only; a steady shape never comes here).  A head is used on one stream at a time.
-        if picks is not None:
-            torch.cuda.current_stream(dev).synchronize()
-        picks = head._modest_roi_targets_picks = torch.zeros((max(2 * B * M, 16),), dtype=torch.int32).pin_memory()
-    return ws, counts, picks
+        torch.cuda.current_stream(dev).synchronize()
+    return ws, counts, pinned_table(head, "_modest_roi_targets_picks", 2 * B * M)
 
 
 def _run(head, batch_dict, cfg):

@@ -258,7 +258,7 @@ def test_header_ctypes_mirror_and_no_scratch():
         assert hasattr(lib, fn)
     res = json.load(open(os.path.join(os.path.dirname(build.LIB), "kernel_resources.json")))
     mine = {k: v for k, v in res.items() if v.get("file") == "post_process.hip"}
-    assert len(mine) == 4 and sum("post_walk" in k for k in mine) == 2 and sum("post_keys" in k for k in mine) == 1 \
+    assert len(mine) == 4 and sum("post_walk" in k for k in mine) == 2 and sum("rank_keysILb1E" in k for k in mine) == 1 \
         and sum("post_recall" in k for k in mine) == 1
     # no scratch memory: no vector register is spilled (a scalar one may move to a vector lane, which costs no memory)
     assert all(v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 for v in mine.values()), mine

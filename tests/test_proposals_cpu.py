@@ -124,9 +124,9 @@ def test_the_cases_cover_the_list():
     st = cases.stats_of(cases.case("past every capacity"))
     assert st[0]["kept"] == st[1]["kept"] == 512 > seq.CHUNK * seq.WAVES and st[0]["chunks"] > seq.WAVES and st[2]["candidates"] == 0
     assert (seq.CHUNK, seq.WAVES, seq.POST_MAX, seq.BATCH_MAX) == (64, 4, 1024, 65535)
-    text = open(os.path.join(ROOT, "modest_amd", "csrc", "proposals.hip")).read()
-    for line in ("constexpr int PW_WAVES = 4;", "constexpr int PW_CHUNK = 64;", "constexpr int PW_POST_MAX = 1024;",
-                 "constexpr int PROP_MAX_BATCH = 65535;"):
+    text = open(os.path.join(ROOT, "modest_amd", "csrc", "prop_walk.h")).read()     # the one place that holds the walk's figures
+    for line in ("constexpr int WK_WAVES = 4;", "constexpr int WK_CHUNK = 64;", "constexpr int WK_POST_MAX = 1024;",
+                 "constexpr int WK_MAX_BATCH = 65535;"):
         assert line in text, line
     # the edges: every limit run, the rows all padding, thresholds on both sides of every IoU
     edge = [cases.case(n) for n in cases.EDGE_CASES]
@@ -337,7 +337,7 @@ def test_header_ctypes_mirror_and_no_scratch():
     assert 24 * n <= lib.modest_proposals_workspace_bytes(n) <= 26 * n
     res = json.load(open(os.path.join(os.path.dirname(build.LIB), "kernel_resources.json")))
     mine = {k: v for k, v in res.items() if v.get("file") == "proposals.hip"}
-    assert len(mine) == 3 and sum("prop_walk" in k for k in mine) == 2 and sum("prop_keys" in k for k in mine) == 1
+    assert len(mine) == 3 and sum("prop_walk" in k for k in mine) == 2 and sum("rank_keysILb0E" in k for k in mine) == 1
     # no scratch memory: no vector register is spilled (a scalar one may move to a vector lane, which costs no memory)
     assert all(v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 for v in mine.values()), mine
     assert max(v["LDS Size [bytes/block]"] for v in mine.values()) <= 160 * 1024
