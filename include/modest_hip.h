@@ -1467,6 +1467,65 @@ int modest_point_decode(int64_t n_rows, int code_in, int num_class, const float 
 int modest_roi_decode(int64_t n_rows, int code, const float *rois_dev, const float *box_preds_dev, float *boxes_dev,
                       void *stream);
 
+/* ---- a38: PointPillars' PillarVFE and BEV scatter with fused backward (csrc/pillar_vfe.hip) -----------
+ * PillarVFE.forward with one PFN layer (features, Linear without bias, BatchNorm1d, ReLU, max over the slots) and
+ * PointPillarScatter.forward, each with its backward.  Every call only enqueues on `stream`: no allocation, no wait on the host,
+ * nothing read back; every output element is written (the canvas: zero-filled, then the rows in range).
+ * voxels (n_pillars, slots, point_features) float32; num_points (n_pillars) and coords (n_pillars, 4) = [b, z, y, x] of the
+ * dtype their code names: 0 float32, 1 int32, 2 int64.  geometry_host: six floats on the HOST, voxel x y z and the offsets
+ * float32(voxel / 2 + range) x y z.  parts: a mask of 1 (the points' own xyz; without it columns 3.. only), 2 (cluster offset),
+ * 4 (centre offset), 8 (distance); the features of a slot, K of them, stand in that order.
+ * Arithmetic: float32, one rounding per operation in the order written, / and sqrt correctly rounded.
+ *   sum_j = v[0][j] + v[1][j] + .. over ALL slots, mean_j = sum_j / float32(num); cluster: v_j - mean_j;
+ *   centre: v_0 - (float32(coord x) vx + xoff) (y with coords[2], z with coords[1]); distance: sqrt((x x + y y) + z z);
+ *   every feature times float32(int(num) > slot): a MULTIPLICATION (num = 0 gives NaN features in every slot);
+ *   x = f_0 W[c][0], then + f_k W[c][k] for k = 1 .. K - 1;  xhat = (x - mean32) invstd32;  t = xhat gamma + beta;
+ *   y = t where t > 0 or t is a NaN, else +0;  out[p][c] = the maximum of y over ALL slots, winner[p][c] its FIRST slot; a NaN
+ *   counts as the maximum and the first NaN wins.
+ * training != 0: mean32 / invstd32 = float32 of mean = sum x / N and 1 / sqrt(var + eps), var = max(sum x x / N - mean mean, 0)
+ *   (a NaN kept), N = n_pillars slots (padded rows count), all float64.  The float64 sums -- sum x, sum x x, sum x f_k per
+ *   channel and sum f_k, kept in sums as [C] [C] [K][C] [K] -- are added over a tree that depends on n_pillars and slots only:
+ *   a wavefront adds modest_pillar_vfe_run() consecutive pillars in pillar then slot order, modest_pillar_vfe_group() such
+ *   partials are added in ascending order, then the groups in ascending order, each from +0.0; x x and x f_k are exact products.
+ *   stat = mean32 [C], invstd32 [C].  The running buffers (NULL: none) are updated in place, in float64 rounded to float32:
+ *   r = (1 - m) r + m new with the unbiased var N / (N - 1) for running_var; m = momentum, or 1 / (tracked + 1) where
+ *   momentum < 0; num_batches_tracked (NULL: none) += 1.  N < 2 is refused, as the reference refuses it.
+ * training == 0: mean32 = running_mean, invstd32 = float32(1 / sqrt(float64(running_var) + eps)); winner may be NULL, sums, stat
+ *   and the workspace are not used and no buffer changes.
+ * modest_pillar_vfe_backward: dy = grad_out where out > 0, else 0, at the winner's slot; over the same tree in float64
+ *   dbeta = sum dy, dgamma = sum dy xhat, A[c][k] = sum dy f_k (exact products), xhat recomputed as in the forward; then with
+ *   g = gamma, mean = float64(mean32), invstd = float64(invstd32):
+ *   dW[c][k] = invstd (((g A) - ((g dbeta) / N) sum f_k) - (((g dgamma) / N) invstd) (sum x f_k - mean sum f_k)), rounded to
+ *   float32 as dgamma and dbeta are.  The voxels get no gradient.
+ * modest_pillar_scatter: canvas (batch, channels, ny, nx) := 0, then canvas[b][c][y][x] = features[p][c] (cell z + y nx + x,
+ *   nz = 1).  A row whose b, z, y or x is out of range (z: other than 0) is skipped.  Two rows of one cell are a precondition
+ *   not to occur.  modest_pillar_scatter_backward: grad_features[p][c] = grad_canvas[b][c][y][x], zeros for a row out of range.
+ * Limits (the call fails and launches nothing): 1 <= out_channels <= 64, 1 <= K <= 16, point_features >= 3, 1 <= slots <= 255,
+ * n_pillars slots <= 2^31 - 1, batch <= 65535, float buffers 4-byte and int64 / float64 buffers 8-byte aligned, a workspace
+ * of modest_pillar_vfe_workspace_bytes(n_pillars, out_channels, K) bytes (negative: a refusal).                              */
+int modest_pillar_vfe_run(void);
+int modest_pillar_vfe_group(void);
+int64_t modest_pillar_vfe_workspace_bytes(int64_t n_pillars, int out_channels, int features);
+int modest_pillar_vfe(int64_t n_pillars, int slots, int point_features, int out_channels, int parts,
+                      const float *voxels_dev, const void *num_points_dev, int num_code, const void *coords_dev,
+                      int coord_code, const float *geometry_host, const float *weight_dev, const float *gamma_dev,
+                      const float *beta_dev, float *running_mean_dev, float *running_var_dev,
+                      int64_t *num_batches_tracked_dev, double eps, double momentum, int training, float *out_dev,
+                      uint8_t *winner_dev, double *sums_dev, float *stat_dev, void *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
+int modest_pillar_vfe_backward(int64_t n_pillars, int slots, int point_features, int out_channels, int parts,
+                               const float *voxels_dev, const void *num_points_dev, int num_code,
+                               const void *coords_dev, int coord_code, const float *geometry_host,
+                               const float *weight_dev, const float *gamma_dev, const float *out_dev,
+                               const uint8_t *winner_dev, const float *grad_out_dev, const double *sums_dev,
+                               const float *stat_dev, float *grad_weight_dev, float *grad_gamma_dev,
+                               float *grad_beta_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_pillar_scatter(int64_t n_pillars, int channels, int batch, int ny, int nx, const float *features_dev,
+                          const void *coords_dev, int coord_code, float *canvas_dev, void *stream);
+int modest_pillar_scatter_backward(int64_t n_pillars, int channels, int batch, int ny, int nx,
+                                   const float *grad_canvas_dev, const void *coords_dev, int coord_code,
+                                   float *grad_features_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

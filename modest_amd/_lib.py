@@ -181,6 +181,15 @@ SIGNATURES = {
     "modest_anchor_decode": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_float, C.c_float, VP, VP]),
     "modest_point_decode": (C.c_int, [C.c_int64, C.c_int, C.c_int, VP, VP, C.c_int64, VP, VP, VP, VP]),
     "modest_roi_decode": (C.c_int, [C.c_int64, C.c_int, VP, VP, VP, VP]),
+    "modest_pillar_vfe_run": (C.c_int, []),
+    "modest_pillar_vfe_group": (C.c_int, []),
+    "modest_pillar_vfe_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "modest_pillar_vfe": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP, VP, VP, VP,
+                                    VP, VP, VP, C.c_double, C.c_double, C.c_int, VP, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_pillar_vfe_backward": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, C.c_int, VP, VP,
+                                             VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int64, VP]),
+    "modest_pillar_scatter": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP]),
+    "modest_pillar_scatter_backward": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP]),
 }
 
 _lib = None

@@ -2374,3 +2374,202 @@ def roi_decode(rois: torch.Tensor, box_preds: torch.Tensor, *, out=None) -> torc
         check(load().modest_roi_decode(R, code, rois.data_ptr(), box_preds.data_ptr(), boxes.data_ptr(), _stream()),
               "modest_roi_decode")
     return boxes
+
+
+# --------------------------------------------------------------------------- PillarVFE and the BEV scatter
+PILLAR_MAX_CHANNELS = 64              # output channels: a lane each
+PILLAR_MAX_FEATURES = 16              # K, the features of a point
+PILLAR_MAX_SLOTS = 255                # the winner is a byte
+PILLAR_MAX_ROWS = (1 << 31) - 1       # P * S
+PILLAR_MAX_BATCH = 65535
+PILLAR_XYZ, PILLAR_CLUSTER, PILLAR_CENTER, PILLAR_DIST = 1, 2, 4, 8      # the parts of a feature row
+_PILLAR_CODES = {torch.float32: 0, torch.int32: 1, torch.int64: 2}      # the dtype codes of voxel_num_points and voxel_coords
+
+
+def pillar_vfe_run() -> int:
+    """pillars whose rows one wavefront sums: the first seam of the partial-sum tree"""
+    return int(load().modest_pillar_vfe_run())
+
+
+def pillar_vfe_group() -> int:
+    """wavefront partials one group sums: the second seam lies at pillar_vfe_run() * pillar_vfe_group() pillars"""
+    return int(load().modest_pillar_vfe_group())
+
+
+def pillar_features(point_features: int, parts: int) -> int:
+    """K, the features of a point, for voxels of `point_features` columns and the mask `parts`"""
+    return ((point_features if parts & PILLAR_XYZ else point_features - 3) + (3 if parts & PILLAR_CLUSTER else 0)
+            + (3 if parts & PILLAR_CENTER else 0) + (1 if parts & PILLAR_DIST else 0))
+
+
+def _pillar_inputs(voxels, num_points, coords, weight, parts, extra=()):
+    """the checks pillar_vfe and pillar_vfe_backward share -> (dev, P, S, Cp, C, K)"""
+    index = (torch.float32, torch.int32, torch.int64)
+    named = (("voxels", voxels), ("voxel_num_points", num_points), ("voxel_coords", coords), ("weight", weight)) + tuple(extra)
+    dev = _device_tensors(named, dtypes={"voxel_num_points": index, "voxel_coords": index, "winner": (torch.uint8,),
+                                         "sums": (torch.float64,), "num_batches_tracked": (torch.int64,)},
+                          optional=[name for name, _ in extra], dtype_error=TypeError, same_device=True)
+    if voxels.ndim != 3 or weight.ndim != 2:
+        raise ValueError(f"voxels {tuple(voxels.shape)} must be (P, S, point features) and weight {tuple(weight.shape)} (C, K)")
+    P, S, Cp = (int(v) for v in voxels.shape)
+    C, K = (int(v) for v in weight.shape)
+    parts = int(parts)
+    if parts < 0 or parts > 15 or Cp < 3:
+        raise ValueError(f"parts = {parts} must be a mask of 1 | 2 | 4 | 8 and voxels need at least 3 point features, got {Cp}")
+    if C < 1 or C > PILLAR_MAX_CHANNELS:
+        raise ValueError(f"C = {C} output channels is outside the limit of 1 .. {PILLAR_MAX_CHANNELS}")
+    if K < 1 or K > PILLAR_MAX_FEATURES:
+        raise ValueError(f"K = {K} features of a point is outside the limit of 1 .. {PILLAR_MAX_FEATURES}")
+    if pillar_features(Cp, parts) != K:
+        raise ValueError(f"weight has K = {K} columns, voxels of {Cp} point features with parts = {parts} make {pillar_features(Cp, parts)}")
+    if S < 1 or S > PILLAR_MAX_SLOTS:
+        raise ValueError(f"S = {S} slots of a pillar is outside the limit of 1 .. {PILLAR_MAX_SLOTS}")
+    if P * S > PILLAR_MAX_ROWS:
+        raise ValueError(f"voxels has P * S = {P * S} rows, above the limit of {PILLAR_MAX_ROWS} rows per call")
+    if tuple(num_points.shape) != (P,) or tuple(coords.shape) != (P, 4):
+        raise ValueError(f"voxel_num_points {tuple(num_points.shape)} and voxel_coords {tuple(coords.shape)} must be ({P},) and ({P}, 4)")
+    for name, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    return dev, P, S, Cp, C, K
+
+
+def _pillar_geometry(voxel_size, offsets):
+    if len(voxel_size) != 3 or len(offsets) != 3:
+        raise ValueError("voxel_size and offsets are three values each")
+    return np.array([float(v) for v in voxel_size] + [float(v) for v in offsets], dtype=np.float32)      # rounded to float32 once
+
+
+def pillar_vfe(voxels: torch.Tensor, num_points: torch.Tensor, coords: torch.Tensor, weight: torch.Tensor, gamma: torch.Tensor,
+               beta: torch.Tensor, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+               num_batches_tracked: Optional[torch.Tensor] = None, *, voxel_size, offsets,
+               parts: int = PILLAR_XYZ | PILLAR_CLUSTER | PILLAR_CENTER, eps: float = 1e-3, momentum: Optional[float] = 0.01,
+               training: bool = True, workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_pillar_vfe on PyTorch's current stream: enqueue only, nothing is read back.
+    voxels (P, S, Cp) float32; num_points (P,) and coords (P, 4) = [b, z, y, x] float32, int32 or int64, read as they are;
+    weight (C, K), gamma and beta (C,) float32; running_mean / running_var (C,) float32 and num_batches_tracked () int64 or None.
+    voxel_size: (vx, vy, vz); offsets: (voxel / 2 + range) x, y, z; both rounded to float32.  momentum None: the cumulative
+    average.  training: batch statistics, and the running buffers are updated IN PLACE; else the running buffers are read.
+    -> (out (P, C) float32, winner (P, C) uint8, sums (2 C + K C + K) float64, stat (2, C) float32 = mean32, invstd32);
+    without `training` winner, sums and stat are None.  `out` = (out, winner, sums, stat) supplies the buffers."""
+    extra = (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var),
+             ("num_batches_tracked", num_batches_tracked))
+    dev, P, S, Cp, C, K = _pillar_inputs(voxels, num_points, coords, weight, parts, extra)
+    if gamma is None or beta is None:
+        raise ValueError("gamma and beta must be device tensors")
+    for name, t in extra[:4]:
+        if t is not None and tuple(t.shape) != (C,):
+            raise ValueError(f"{name} {tuple(t.shape)} must be (C,) = ({C},)")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    if not training and running_mean is None:
+        raise ValueError("eval mode needs running_mean and running_var")
+    if num_batches_tracked is not None and num_batches_tracked.numel() != 1:
+        raise ValueError("num_batches_tracked must hold one int64")
+    if training and P * S < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got P * S = {P * S} rows")
+    geometry = _pillar_geometry(voxel_size, offsets)
+    Q = 2 * C + K * C + K
+    res, winner, sums, stat = _outputs((("out", torch.float32, (P, C), True), ("winner", torch.uint8, (P, C), training),
+                                        ("sums", torch.float64, (Q,), training), ("stat", torch.float32, (2, C), training)),
+                                       out, dev, absent=("is not due in eval mode", "must be a tensor"))
+    if training:
+        workspace = _workspace(_workspace_bytes("modest_pillar_vfe_workspace_bytes", P, C, K), workspace, dev)
+    ptr = _ptr
+    with torch.cuda.device(dev):
+        check(load().modest_pillar_vfe(P, S, Cp, C, int(parts), ptr(voxels), ptr(num_points), _PILLAR_CODES[num_points.dtype],
+                                       ptr(coords), _PILLAR_CODES[coords.dtype], geometry.ctypes.data, ptr(weight), ptr(gamma),
+                                       ptr(beta), ptr(running_mean), ptr(running_var), ptr(num_batches_tracked) if training else None,
+                                       float(eps), -1.0 if momentum is None else float(momentum), int(bool(training)), ptr(res),
+                                       ptr(winner), ptr(sums), ptr(stat), ptr(workspace) if training else None,
+                                       workspace.numel() if training else 0, _stream()), "modest_pillar_vfe")
+    return res, winner, sums, stat
+
+
+def pillar_vfe_backward(voxels: torch.Tensor, num_points: torch.Tensor, coords: torch.Tensor, weight: torch.Tensor,
+                        gamma: torch.Tensor, out_features: torch.Tensor, winner: torch.Tensor, grad_out: torch.Tensor,
+                        sums: torch.Tensor, stat: torch.Tensor, *, voxel_size, offsets,
+                        parts: int = PILLAR_XYZ | PILLAR_CLUSTER | PILLAR_CENTER, workspace: Optional[torch.Tensor] = None, out=None):
+    """modest_pillar_vfe_backward on PyTorch's current stream: enqueue only, nothing is read back.
+    The inputs of `pillar_vfe` as they were, what it returned in training mode (out_features, winner, sums, stat) and grad_out
+    (P, C) float32.  -> (grad_weight (C, K), grad_gamma (C,), grad_beta (C,)) float32 (`out` supplies them), every element
+    written.  The voxels get no gradient."""
+    extra = (("gamma", gamma), ("out_features", out_features), ("winner", winner), ("grad_out", grad_out), ("sums", sums), ("stat", stat))
+    dev, P, S, Cp, C, K = _pillar_inputs(voxels, num_points, coords, weight, parts, extra)
+    Q = 2 * C + K * C + K
+    for name, t, shape in (("gamma", gamma, (C,)), ("out_features", out_features, (P, C)), ("winner", winner, (P, C)),
+                           ("grad_out", grad_out, (P, C)), ("sums", sums, (Q,)), ("stat", stat, (2, C))):
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a {shape} tensor" + ("" if t is None else f", got {tuple(t.shape)}"))
+    if P * S < 2:
+        raise ValueError(f"the backward of a training forward needs more than 1 row, got P * S = {P * S}")
+    geometry = _pillar_geometry(voxel_size, offsets)
+    dW, dg, db = _outputs((("grad_weight", torch.float32, (C, K), True), ("grad_gamma", torch.float32, (C,), True),
+                           ("grad_beta", torch.float32, (C,), True)), out, dev)
+    workspace = _workspace(_workspace_bytes("modest_pillar_vfe_workspace_bytes", P, C, K), workspace, dev)
+    ptr = _ptr
+    with torch.cuda.device(dev):
+        check(load().modest_pillar_vfe_backward(P, S, Cp, C, int(parts), ptr(voxels), ptr(num_points), _PILLAR_CODES[num_points.dtype],
+                                                ptr(coords), _PILLAR_CODES[coords.dtype], geometry.ctypes.data, ptr(weight),
+                                                ptr(gamma), ptr(out_features), ptr(winner), ptr(grad_out), ptr(sums), ptr(stat),
+                                                ptr(dW), ptr(dg), ptr(db), ptr(workspace), workspace.numel(), _stream()),
+              "modest_pillar_vfe_backward")
+    return dW, dg, db
+
+
+def _scatter_inputs(rows, rows_name, coords, batch_size, ny, nx):
+    index = (torch.float32, torch.int32, torch.int64)
+    dev = _device_tensors(((rows_name, rows), ("voxel_coords", coords)), dtypes={"voxel_coords": index}, dtype_error=TypeError,
+                          same_device=True)
+    B, ny, nx = int(batch_size), int(ny), int(nx)
+    if B < 0 or B > PILLAR_MAX_BATCH:
+        raise ValueError(f"batch_size = {B} is outside the limit of 0 .. {PILLAR_MAX_BATCH}")
+    if ny < 1 or nx < 1 or ny * nx > PILLAR_MAX_ROWS:
+        raise ValueError(f"a grid of ny = {ny}, nx = {nx} must have between 1 and {PILLAR_MAX_ROWS} cells")
+    return dev, B, ny, nx
+
+
+def pillar_scatter(features: torch.Tensor, coords: torch.Tensor, batch_size: int, ny: int, nx: int, *, out=None) -> torch.Tensor:
+    """modest_pillar_scatter on PyTorch's current stream: enqueue only, nothing is read back.
+    features (P, C) float32, coords (P, 4) = [b, z, y, x] float32, int32 or int64, contiguous.
+    -> canvas (batch_size, C, ny, nx) float32 (`out` supplies it): zeros, then canvas[b, c, y, x] = features[p, c]; a row whose b,
+    z, y or x is out of range (nz = 1) is skipped.  Two rows of one cell must not occur."""
+    dev, B, ny, nx = _scatter_inputs(features, "pillar_features", coords, batch_size, ny, nx)
+    if features.ndim != 2 or tuple(coords.shape) != (int(features.shape[0]), 4):
+        raise ValueError(f"pillar_features {tuple(features.shape)} and voxel_coords {tuple(coords.shape)} must be (P, C) and (P, 4)")
+    P, C = (int(v) for v in features.shape)
+    if C < 1 or C > PILLAR_MAX_CHANNELS:
+        raise ValueError(f"C = {C} channels is outside the limit of 1 .. {PILLAR_MAX_CHANNELS}")
+    for name, t in (("pillar_features", features), ("voxel_coords", coords)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    canvas = _decode_out(out, (B, C, ny, nx), dev)
+    with torch.cuda.device(dev):
+        check(load().modest_pillar_scatter(P, C, B, ny, nx, _ptr_filled(features), _ptr_filled(coords), _PILLAR_CODES[coords.dtype],
+                                           _ptr_filled(canvas), _stream()), "modest_pillar_scatter")
+    return canvas
+
+
+def pillar_scatter_backward(grad_canvas: torch.Tensor, coords: torch.Tensor, *, out=None) -> torch.Tensor:
+    """modest_pillar_scatter_backward on PyTorch's current stream: enqueue only, nothing is read back.
+    grad_canvas (B, C, ny, nx) float32 contiguous, coords (P, 4) as pillar_scatter read them.
+    -> grad_features (P, C) float32 (`out` supplies it), every element written: grad_canvas[b, :, y, x], zeros for a row out of
+    range."""
+    if not torch.is_tensor(grad_canvas) or grad_canvas.ndim != 4:
+        raise ValueError("grad_canvas must be a (B, C, ny, nx) device tensor (PyTorch-ROCm 'cuda')")
+    B, C, ny, nx = (int(v) for v in grad_canvas.shape)
+    dev, B, ny, nx = _scatter_inputs(grad_canvas, "grad_canvas", coords, B, max(ny, 1), max(nx, 1))
+    if coords.ndim != 2 or int(coords.shape[1]) != 4:
+        raise ValueError(f"voxel_coords {tuple(coords.shape)} must be (P, 4)")
+    P = int(coords.shape[0])
+    if C < 1 or C > PILLAR_MAX_CHANNELS:
+        raise ValueError(f"C = {C} channels is outside the limit of 1 .. {PILLAR_MAX_CHANNELS}")
+    for name, t in (("grad_canvas", grad_canvas), ("voxel_coords", coords)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+    grad = _decode_out(out, (P, C), dev)
+    with torch.cuda.device(dev):
+        check(load().modest_pillar_scatter_backward(P, C, B, ny, nx, _ptr_filled(grad_canvas), _ptr_filled(coords),
+                                                    _PILLAR_CODES[coords.dtype], _ptr_filled(grad), _stream()),
+              "modest_pillar_scatter_backward")
+    return grad

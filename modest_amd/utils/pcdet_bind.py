@@ -70,6 +70,12 @@ class defines its own ``get_loss``, so binding the template would do nothing); a
 ``modest_amd.utils.box_decode`` -- the box decoding of every head in one call each -- on
 ``AnchorHeadTemplate``, ``PointHeadTemplate`` and ``RoIHeadTemplate``, whose modules are imported for it if they are not yet; a
 head that overrides ``generate_predicted_boxes`` itself keeps its own.  The decoded boxes carry no ``grad_fn``.
+
+``bind_pillar_vfe()``, a function of its own like the others, sets the two ``forward`` of ``modest_amd.utils.pillar_vfe`` --
+PointPillars' feature encoder and BEV scatter with their fused backward -- on ``PillarVFE`` of
+``pcdet.models.backbones_3d.vfe.pillar_vfe`` and ``PointPillarScatter`` of
+``pcdet.models.backbones_2d.map_to_bev.pointpillar_scatter``, whose modules are imported for it if they are not yet; a subclass
+that overrides ``forward`` keeps its own.  Parameters, buffers and ``state_dict`` stay the modules' own.
 """
 import importlib
 import importlib.util
@@ -115,6 +121,9 @@ BOX_DECODE_NAMES = {"pcdet.models.dense_heads.anchor_head_template": "AnchorHead
                     "pcdet.models.dense_heads.point_head_template": "PointHeadTemplate",
                     "pcdet.models.roi_heads.roi_head_template": "RoIHeadTemplate"}
 BOX_DECODE = "modest_amd.utils.box_decode"             # its methods set on the three templates by bind_box_decode()
+PILLAR_VFE_NAMES = {"pcdet.models.backbones_3d.vfe.pillar_vfe": "PillarVFE",
+                    "pcdet.models.backbones_2d.map_to_bev.pointpillar_scatter": "PointPillarScatter"}
+PILLAR_VFE = "modest_amd.utils.pillar_vfe"             # its two forward methods set on the two classes by bind_pillar_vfe()
 
 
 class StandIn(types.ModuleType):
@@ -275,6 +284,16 @@ def bind_box_decode():
     overrides generate_predicted_boxes keeps its own.  A module that lacks its class is skipped.  Idempotent; before or after
     ``import pcdet.models``; touches no GPU state."""
     return _bind_onto_each(BOX_DECODE_NAMES, BOX_DECODE, with_class_name=True)
+
+
+def bind_pillar_vfe():
+    """PillarVFE / PointPillarScatter .forward := the two methods of modest_amd.utils.pillar_vfe -- PointPillars' feature encoder
+    and BEV scatter with their fused backward -- in the reference's modules where they are imported or
+    can be -> {module name: module} of the modules bound, or None where pcdet cannot be imported.  A function of its own:
+    install() and what it returns stay as they are.  Only the two classes' own methods are set, so a subclass that overrides
+    forward keeps its own; parameters and buffers are untouched.  A module that lacks its class is skipped.  Idempotent; before
+    or after ``import pcdet.models``; touches no GPU state."""
+    return _bind_onto_each(PILLAR_VFE_NAMES, PILLAR_VFE, with_class_name=True)
 
 
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
