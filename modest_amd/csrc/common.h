@@ -150,3 +150,5 @@ struct Arena {
 static inline size_t arena_sz(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+constexpr int64_t GRID_MAX = 2147483647;   // workgroups of a one-dimensional grid: entry points refuse more

@@ -14,14 +14,16 @@
 //     may differ in the last bits).
 // Every element offset is 64-bit.  An index outside [0, N) (the reference would read or write out of bounds) is
 // skipped by the gradients and reads as 0 in the forward gathers.
+// The ball walk with its placing and padding of the hits, and the tile walk and merge of three-NN, are pn2_search.h's,
+// shared with the stacked layout (pointnet2_stack.hip); the kernels here resolve a cloud's pointers and store.
 #include <hip/hip_runtime.h>
-#include <limits.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "common.h"
 #include "modest_hip.h"
+#include "pn2_search.h"
 
 namespace {
 
@@ -168,9 +170,7 @@ __global__ __launch_bounds__(1024) void pn2_fps_global(int n, int m, int L, int 
 }
 
 // ---------------------------------------------------------------- ball query ---------------------------------------
-// A wavefront per centre: 64 consecutive points per step (four steps in flight), ballot + prefix popcount put the hits
-// at their place in index order, the walk ends once nsample are found.
-constexpr int BQ_UNROLL = 4;
+// A wavefront per centre; the walk, the order of the hits and the padding are pn2_search.h's.
 __global__ __launch_bounds__(256) void pn2_ball_query(int64_t centres, int n, int m, float r2, int nsample,
                                                       const float *__restrict__ new_xyz, const float *__restrict__ xyz,
                                                       int32_t *__restrict__ idx) {
@@ -182,100 +182,30 @@ __global__ __launch_bounds__(256) void pn2_ball_query(int64_t centres, int n, in
     const float *p = xyz + b * n * 3;
     int32_t *out = idx + w * nsample;
     const unsigned long long below = (1ull << lane) - 1ull;
-    int cnt = 0, first = -1;
-    for (int k0 = 0; k0 < n && cnt < nsample; k0 += 64 * BQ_UNROLL) {
-        bool hit[BQ_UNROLL];
-#pragma unroll
-        for (int u = 0; u < BQ_UNROLL; ++u) {
-            const int k = k0 + u * 64 + lane;
-            hit[u] = false;
-            if (k < n) {
-                const float x = p[(int64_t)k * 3 + 0], y = p[(int64_t)k * 3 + 1], z = p[(int64_t)k * 3 + 2];
-                const float d2 = ((cx - x) * (cx - x) + (cy - y) * (cy - y)) + (cz - z) * (cz - z);
-                hit[u] = d2 < r2;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < BQ_UNROLL; ++u) {
-            const unsigned long long mask = __ballot(hit[u]);
-            if (mask && cnt < nsample) {
-                if (first < 0) first = k0 + u * 64 + (__ffsll((long long)mask) - 1);
-                const int pos = cnt + __popcll(mask & below);
-                if (hit[u] && pos < nsample) out[pos] = k0 + u * 64 + lane;
-                cnt += __popcll(mask);
-            }
-        }
-    }
-    if (cnt > 0)
-        for (int l = cnt + lane; l < nsample; l += 64) out[l] = first;
+    const Pn2Row row = pn2_ball_walk(p, n, cx, cy, cz, r2, lane, below, nsample, out);
+    if (row.cnt > 0) pn2_pad_row(lane, row, nsample, out);   // a row without a hit stays as the caller gave it
 }
 
 // ---------------------------------------------------------------- three nearest neighbours ------------------------
-// 64 unknown points per workgroup, one per lane; the known points pass through LDS in tiles and each of the four
-// wavefronts walks its quarter of every tile in index order (all lanes read one address: a broadcast), keeping its own
-// best three with the reference's strict <.  The reference's result is the three smallest (distance, index) pairs in
-// lexicographic order, so the four lists merge exactly by that order; a slot never filled travels as (inf, INT_MAX),
-// behind any real pair, and leaves as the reference's initial values (1e40 -> inf, index 0).
-constexpr int NN_TILE = 1024, NN_PARTS = 4, NN_SEG = NN_TILE / NN_PARTS;
-__device__ __forceinline__ bool nn_less(float a, int ia, float b, int ib) { return a < b || (a == b && ia < ib); }
+// 64 unknown points of one cloud per workgroup, one per lane, against the cloud's m known points: one range for
+// pn2_search.h's tile walk, every lane compares, and the merged result is stored as it is.
 __global__ __launch_bounds__(256) void pn2_three_nn(int n, int m, int blocks_per_cloud, const float *__restrict__ unknown,
                                                     const float *__restrict__ known, float *__restrict__ dist2,
                                                     int32_t *__restrict__ idx) {
     __shared__ float sk[NN_TILE * 3];
     __shared__ float md[NN_PARTS - 1][3][64];
     __shared__ int mi[NN_PARTS - 1][3][64];
-    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int64_t b = blockIdx.x / blocks_per_cloud;
     const int pt = (int)(blockIdx.x % blocks_per_cloud) * 64 + lane;
     const bool ok = pt < n;
     const int64_t u = (b * n + (ok ? pt : 0)) * 3;
     const float ux = unknown[u + 0], uy = unknown[u + 1], uz = unknown[u + 2];
-    const float *kn = known + b * m * 3;
-    double best1 = 1e40, best2 = 1e40, best3 = 1e40;
-    int i1 = 0, i2 = 0, i3 = 0;
-    for (int k0 = 0; k0 < m; k0 += NN_TILE) {
-        const int cnt = min(NN_TILE, m - k0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < cnt * 3; i += 256) sk[i] = kn[(int64_t)k0 * 3 + i];
-        __syncthreads();
-        const int s0 = part * NN_SEG, s1 = min(cnt, s0 + NN_SEG);
-#pragma unroll 8
-        for (int k = s0; k < s1; ++k) {
-            const float x = sk[k * 3 + 0], y = sk[k * 3 + 1], z = sk[k * 3 + 2];
-            const float d = ((ux - x) * (ux - x) + (uy - y) * (uy - y)) + (uz - z) * (uz - z);
-            if (d < best1) {
-                best3 = best2; i3 = i2;
-                best2 = best1; i2 = i1;
-                best1 = d; i1 = k0 + k;
-            } else if (d < best2) {
-                best3 = best2; i3 = i2;
-                best2 = d; i2 = k0 + k;
-            } else if (d < best3) {
-                best3 = d; i3 = k0 + k;
-            }
-        }
-    }
-    float d1 = (float)best1, d2 = (float)best2, d3 = (float)best3;
-    if (best1 == 1e40) i1 = INT_MAX;
-    if (best2 == 1e40) i2 = INT_MAX;
-    if (best3 == 1e40) i3 = INT_MAX;
-    if (part > 0) {
-        md[part - 1][0][lane] = d1; md[part - 1][1][lane] = d2; md[part - 1][2][lane] = d3;
-        mi[part - 1][0][lane] = i1; mi[part - 1][1][lane] = i2; mi[part - 1][2][lane] = i3;
-    }
-    __syncthreads();
-    if (part == 0 && ok) {
-#pragma unroll
-        for (int q = 0; q < (NN_PARTS - 1) * 3; ++q) {
-            const float d = md[q / 3][q % 3][lane];
-            const int i = mi[q / 3][q % 3][lane];
-            const bool l1 = nn_less(d, i, d1, i1), l2 = nn_less(d, i, d2, i2), l3 = nn_less(d, i, d3, i3);
-            d3 = l2 ? d2 : (l3 ? d : d3); i3 = l2 ? i2 : (l3 ? i : i3);
-            d2 = l1 ? d1 : (l2 ? d : d2); i2 = l1 ? i1 : (l2 ? i : i2);
-            d1 = l1 ? d : d1; i1 = l1 ? i : i1;
-        }
-        dist2[u + 0] = d1; dist2[u + 1] = d2; dist2[u + 2] = d3;
-        idx[u + 0] = i1 == INT_MAX ? 0 : i1; idx[u + 1] = i2 == INT_MAX ? 0 : i2; idx[u + 2] = i3 == INT_MAX ? 0 : i3;
+    const NNBest best = nn_walk(known + b * m * 3, m, true, ux, uy, uz, sk, threadIdx.x >> 6, NN_NONE);
+    NNResult r;
+    if (nn_finish(best, ok, md, mi, r)) {
+        dist2[u + 0] = r.d1; dist2[u + 1] = r.d2; dist2[u + 2] = r.d3;
+        idx[u + 0] = r.i1; idx[u + 1] = r.i2; idx[u + 2] = r.i3;
     }
 }
 
@@ -396,7 +326,6 @@ __global__ __launch_bounds__(256) void pn2_scatter_atomic(int c, int n, int64_t 
 constexpr int SC_SMALL = 8192, SC_LARGE = 36864;   // 32 KB (several workgroups per CU) and 144 KB of the CU's 160 KB
 constexpr int SC_MAX_ROWS = 16;
 constexpr int SC_FILL = 256, SC_MIN_TERMS = 4096;
-constexpr int64_t GRID_MAX = 2147483647;
 
 template <bool WEIGHTED>
 int scatter_launch(int b, int c, int n, int64_t K, const float *go, const int32_t *idx, const float *weight, float *grad,

@@ -21,6 +21,9 @@
 //     they are given with global float atomics (two runs may differ in the last bits), an element no term reaches is
 //     not written.
 // Every element offset is 64-bit.
+// The ball walk, the placing and padding of the hits (both queries) and the tile walk and merge of three-NN are
+// pn2_search.h's, shared with the batch layout (pointnet2.hip); the kernels here find a row's scan, and own the -1 of a
+// row without a hit and the scan's start added to a three-NN index.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -29,10 +32,9 @@
 
 #include "common.h"
 #include "modest_hip.h"
+#include "pn2_search.h"
 
 namespace {
-
-constexpr int64_t GRID_MAX = 2147483647;
 
 // ---------------------------------------------------------------- the scan of a row --------------------------------
 __device__ __forceinline__ int64_t cnt_at(const int32_t *cnt, int k) { return (int64_t)max(cnt[k], 0); }
@@ -77,10 +79,8 @@ __device__ __forceinline__ ScanPos find_scan(int64_t p, int b_total, const int32
 }
 
 // ---------------------------------------------------------------- ball query ---------------------------------------
-// A wavefront per centre, as pn2_ball_query: 64 consecutive points of the centre's scan per step (four steps in
-// flight), ballot + prefix popcount put the hits at their place in index order, the walk ends once nsample are found.
+// A wavefront per centre: pn2_search.h's walk over the points of the centre's scan, so the indices are scan-local.
 // Each wavefront resolves its own centre's scan, so a workgroup whose four centres straddle two scans needs no care.
-constexpr int Q_UNROLL = 4;
 __global__ __launch_bounds__(256) void pn2s_ball_query(int b_total, int64_t m, int64_t n_rows, float r2, int nsample,
                                                        const float *__restrict__ new_xyz,
                                                        const int32_t *__restrict__ new_cnt,
@@ -96,32 +96,9 @@ __global__ __launch_bounds__(256) void pn2s_ball_query(int b_total, int64_t m, i
     const float *p = xyz + lo * 3;
     int32_t *out = idx + w * nsample;
     const unsigned long long below = (1ull << lane) - 1ull;
-    int cnt = 0, first = -1;
-    for (int k0 = 0; k0 < n && cnt < nsample; k0 += 64 * Q_UNROLL) {
-        bool hit[Q_UNROLL];
-#pragma unroll
-        for (int u = 0; u < Q_UNROLL; ++u) {
-            const int k = k0 + u * 64 + lane;
-            hit[u] = false;
-            if (k < n) {
-                const float x = p[(int64_t)k * 3 + 0], y = p[(int64_t)k * 3 + 1], z = p[(int64_t)k * 3 + 2];
-                const float d2 = ((cx - x) * (cx - x) + (cy - y) * (cy - y)) + (cz - z) * (cz - z);
-                hit[u] = d2 < r2;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < Q_UNROLL; ++u) {
-            const unsigned long long mask = __ballot(hit[u]);
-            if (mask && cnt < nsample) {
-                if (first < 0) first = k0 + u * 64 + (__ffsll((long long)mask) - 1);
-                const int pos = cnt + __popcll(mask & below);
-                if (hit[u] && pos < nsample) out[pos] = k0 + u * 64 + lane;
-                cnt += __popcll(mask);
-            }
-        }
-    }
-    if (cnt > 0) {
-        for (int l = cnt + lane; l < nsample; l += 64) out[l] = first;
+    const Pn2Row row = pn2_ball_walk(p, n, cx, cy, cz, r2, lane, below, nsample, out);
+    if (row.cnt > 0) {
+        pn2_pad_row(lane, row, nsample, out);
     } else if (lane == 0) {
         out[0] = -1;
     }
@@ -130,7 +107,8 @@ __global__ __launch_bounds__(256) void pn2s_ball_query(int b_total, int64_t m, i
 // ---------------------------------------------------------------- voxel query --------------------------------------
 // A wavefront per query.  The (2rz+1)(2ry+1)(2rx+1) box is first clipped to the grid (the cells cut off are the ones the
 // reference skips, so the visiting order of the rest is unchanged); lanes take 64 consecutive cells of the clipped box in
-// dz, dy, dx order, and the same ballot compaction keeps the accepted ones in the serial order.
+// dz, dy, dx order, and pn2_search.h's placing of the hits keeps the accepted ones in the serial order; the value a
+// lane writes is the row its cell holds, not its position.
 __global__ __launch_bounds__(256) void pn2s_voxel_query(int64_t m, int b_total, int r1, int r2_, int r3, int nsample,
                                                         float rad2, int rz, int ry, int rx, int64_t n_rows,
                                                         const float *__restrict__ new_xyz, const float *__restrict__ xyz,
@@ -147,15 +125,15 @@ __global__ __launch_bounds__(256) void pn2s_voxel_query(int64_t m, int b_total, 
     const int64_t z0 = max(cz - rz, (int64_t)0), z1 = min(cz + rz, (int64_t)r1 - 1);
     const int64_t y0 = max(cy - ry, (int64_t)0), y1 = min(cy + ry, (int64_t)r2_ - 1);
     const int64_t x0 = max(cx - rx, (int64_t)0), x1 = min(cx + rx, (int64_t)r3 - 1);
-    int cnt = 0, first = -1;
+    Pn2Row row = PN2_NO_HIT;
     if ((unsigned)bi < (unsigned)b_total && z0 <= z1 && y0 <= y1 && x0 <= x1) {
         const int ny = (int)(y1 - y0 + 1), nx = (int)(x1 - x0 + 1);
         const int cells = (int)(z1 - z0 + 1) * ny * nx;   // <= the product the entry point bounded by INT_MAX
-        for (int64_t t0 = 0; t0 < cells && cnt < nsample; t0 += 64 * Q_UNROLL) {
-            bool hit[Q_UNROLL];
-            int nb[Q_UNROLL];
+        for (int64_t t0 = 0; t0 < cells && row.cnt < nsample; t0 += 64 * PN2_UNROLL) {
+            bool hit[PN2_UNROLL];
+            int nb[PN2_UNROLL];
 #pragma unroll
-            for (int u = 0; u < Q_UNROLL; ++u) {
+            for (int u = 0; u < PN2_UNROLL; ++u) {
                 const int64_t t = t0 + u * 64 + lane;
                 hit[u] = false;
                 nb[u] = -1;
@@ -172,33 +150,25 @@ __global__ __launch_bounds__(256) void pn2s_voxel_query(int64_t m, int b_total, 
                 }
             }
 #pragma unroll
-            for (int u = 0; u < Q_UNROLL; ++u) {
-                const unsigned long long mask = __ballot(hit[u]);
-                if (mask && cnt < nsample) {
-                    if (first < 0) first = __shfl(nb[u], __ffsll((long long)mask) - 1);
-                    const int pos = cnt + __popcll(mask & below);
-                    if (hit[u] && pos < nsample) out[pos] = nb[u];
-                    cnt += __popcll(mask);
-                }
+            for (int u = 0; u < PN2_UNROLL; ++u) {
+                const int v = nb[u];
+                row = pn2_place_hits(hit[u], v, [v](int j) { return __shfl(v, j); }, below, nsample, row, out);
             }
         }
     }
-    if (cnt > 0) {
-        for (int l = cnt + lane; l < nsample; l += 64) out[l] = first;
+    if (row.cnt > 0) {
+        pn2_pad_row(lane, row, nsample, out);
     } else if (lane == 0) {
         out[0] = -1;
     }
 }
 
 // ---------------------------------------------------------------- three nearest neighbours ------------------------
-// The tile design of pn2_three_nn: 64 unknown rows per workgroup, one per lane; the known points pass through LDS in
-// tiles and each of the four wavefronts walks its quarter of every tile in index order, keeping its own best three with
-// the reference's strict <; the four lists merge by (distance, index).  The 64 rows may lie in several scans: the
-// workgroup finds the scan of its first row and then walks the scans in order until its last row is behind it; in each
-// scan only the lanes whose row belongs to it compare.  A row belongs to exactly one scan, so its best three are from that
-// scan's known rows alone.
-constexpr int NN_TILE = 1024, NN_PARTS = 4, NN_SEG = NN_TILE / NN_PARTS;
-__device__ __forceinline__ bool nn_less(float a, int ia, float b, int ib) { return a < b || (a == b && ia < ib); }
+// 64 unknown rows per workgroup, one per lane, on pn2_search.h's tile walk and merge.  The 64 rows may lie in several
+// scans: the workgroup finds the scan of its first row and then walks the scans in order until its last row is behind it,
+// one range of known rows per scan; in each only the lanes whose row belongs to the scan compare.  A row belongs to
+// exactly one scan, so its best three are from that scan's known rows alone, counted from the scan's first known row:
+// my_start makes them global.  The loop conditions around the walk are the same in every lane (the walk has barriers).
 __global__ __launch_bounds__(256) void pn2s_three_nn(int b_total, int64_t n, int64_t m_rows,
                                                      const float *__restrict__ unknown,
                                                      const int32_t *__restrict__ unknown_cnt,
@@ -208,13 +178,12 @@ __global__ __launch_bounds__(256) void pn2s_three_nn(int b_total, int64_t n, int
     __shared__ float sk[NN_TILE * 3];
     __shared__ float md[NN_PARTS - 1][3][64];
     __shared__ int mi[NN_PARTS - 1][3][64];
-    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int64_t row0 = (int64_t)blockIdx.x * 64, pt = row0 + lane, last_row = min(n - 1, row0 + 63);
     const bool ok = pt < n;
     const int64_t u = (ok ? pt : row0) * 3;
     const float ux = unknown[u + 0], uy = unknown[u + 1], uz = unknown[u + 2];
-    double best1 = 1e40, best2 = 1e40, best3 = 1e40;
-    int i1 = 0, i2 = 0, i3 = 0;
+    NNBest best = NN_NONE;
     int64_t my_start = 0;
     const ScanPos sp = find_scan(row0, b_total, unknown_cnt, known_cnt);
     int64_t qs = sp.qstart, xs = sp.xstart;
@@ -225,58 +194,17 @@ __global__ __launch_bounds__(256) void pn2s_three_nn(int b_total, int64_t n, int
         if (last || (cq > 0 && qs + cq > row0)) {   // the scan holds rows of this workgroup (the same answer in every lane)
             if (mine) my_start = xs;
             const int64_t lo = min(xs, m_rows), kn = min(cx, m_rows - lo);
-            const float *kp = known + lo * 3;
-            for (int64_t k0 = 0; k0 < kn; k0 += NN_TILE) {
-                const int cnt = (int)min((int64_t)NN_TILE, kn - k0);
-                __syncthreads();
-                for (int i = threadIdx.x; i < cnt * 3; i += 256) sk[i] = kp[k0 * 3 + i];
-                __syncthreads();
-                if (mine) {
-                    const int s0 = part * NN_SEG, s1 = min(cnt, s0 + NN_SEG);
-#pragma unroll 8
-                    for (int k = s0; k < s1; ++k) {
-                        const float x = sk[k * 3 + 0], y = sk[k * 3 + 1], z = sk[k * 3 + 2];
-                        const float d = ((ux - x) * (ux - x) + (uy - y) * (uy - y)) + (uz - z) * (uz - z);
-                        if (d < best1) {
-                            best3 = best2; i3 = i2;
-                            best2 = best1; i2 = i1;
-                            best1 = d; i1 = (int)k0 + k;
-                        } else if (d < best2) {
-                            best3 = best2; i3 = i2;
-                            best2 = d; i2 = (int)k0 + k;
-                        } else if (d < best3) {
-                            best3 = d; i3 = (int)k0 + k;
-                        }
-                    }
-                }
-            }
+            best = nn_walk(known + lo * 3, kn, mine, ux, uy, uz, sk, threadIdx.x >> 6, best);
         }
         qs += cq;
         xs += cx;
     }
-    float d1 = (float)best1, d2 = (float)best2, d3 = (float)best3;
-    if (best1 == 1e40) i1 = INT_MAX;
-    if (best2 == 1e40) i2 = INT_MAX;
-    if (best3 == 1e40) i3 = INT_MAX;
-    if (part > 0) {
-        md[part - 1][0][lane] = d1; md[part - 1][1][lane] = d2; md[part - 1][2][lane] = d3;
-        mi[part - 1][0][lane] = i1; mi[part - 1][1][lane] = i2; mi[part - 1][2][lane] = i3;
-    }
-    __syncthreads();
-    if (part == 0 && ok) {
-#pragma unroll
-        for (int q = 0; q < (NN_PARTS - 1) * 3; ++q) {
-            const float d = md[q / 3][q % 3][lane];
-            const int i = mi[q / 3][q % 3][lane];
-            const bool l1 = nn_less(d, i, d1, i1), l2 = nn_less(d, i, d2, i2), l3 = nn_less(d, i, d3, i3);
-            d3 = l2 ? d2 : (l3 ? d : d3); i3 = l2 ? i2 : (l3 ? i : i3);
-            d2 = l1 ? d1 : (l2 ? d : d2); i2 = l1 ? i1 : (l2 ? i : i2);
-            d1 = l1 ? d : d1; i1 = l1 ? i : i1;
-        }
-        dist2[u + 0] = d1; dist2[u + 1] = d2; dist2[u + 2] = d3;
-        idx[u + 0] = (int32_t)(my_start + (i1 == INT_MAX ? 0 : i1));
-        idx[u + 1] = (int32_t)(my_start + (i2 == INT_MAX ? 0 : i2));
-        idx[u + 2] = (int32_t)(my_start + (i3 == INT_MAX ? 0 : i3));
+    NNResult r;
+    if (nn_finish(best, ok, md, mi, r)) {
+        dist2[u + 0] = r.d1; dist2[u + 1] = r.d2; dist2[u + 2] = r.d3;
+        idx[u + 0] = (int32_t)(my_start + r.i1);
+        idx[u + 1] = (int32_t)(my_start + r.i2);
+        idx[u + 2] = (int32_t)(my_start + r.i3);
     }
 }
 

@@ -23,8 +23,6 @@
 
 namespace {
 
-constexpr int64_t GRID_MAX = 2147483647;
-
 // min(max((unsigned)(int)q, 0), out - 1) of the reference, its cases written out: nothing here converts a NaN or an
 // out-of-range float to int.  1 <= out <= 256.
 __device__ __forceinline__ int voxel_index(float q, int out) {

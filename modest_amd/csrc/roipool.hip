@@ -29,8 +29,6 @@
 
 namespace {
 
-constexpr int64_t GRID_MAX = 2147483647;
-
 // ---------------------------------------------------------------- RoI point pooling -------------------------------
 // One workgroup of four wavefronts per (cloud, box); the box's terms are computed once (every lane the same values, in
 // registers).  The cloud is walked in index order in chunks of 1024 points = 16 sub-blocks of 64; wavefront w takes the

@@ -2,63 +2,15 @@
 (``pcdet/ops/pointnet2/pointnet2_batch/src/pointnet2_api.cpp:10-24``): the same nine
 functions with the same integer and tensor arguments and return value 1, forwarded to
 the C ABI of libmodest_hip.so on the current torch stream.  The reference checks
-nothing; here a tensor that is not a contiguous CUDA tensor of the expected dtype, or
-whose shape contradicts the integer arguments, raises ``RuntimeError``.
+nothing; here a tensor that is not a contiguous CUDA tensor of the expected dtype, whose
+shape contradicts the integer arguments or has a dimension above 2^31 - 1 raises
+``RuntimeError`` (the checks all drop-ins share, ``modest_amd/utils/_ext.py``).
 
 Bound as ``sys.modules["pcdet.ops.pointnet2.pointnet2_batch.pointnet2_batch_cuda"]``
 (INTEGRATION.md), OpenPCDet's own ``pointnet2_utils.py`` / ``pointnet2_modules.py`` run
 on top of it unchanged.
 """
-import torch as _torch
-
-from .... import _lib
-
-
-def _t(t, name, dtype, shape):
-    if not isinstance(t, _torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be CUDA tensor")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be contiguous tensor")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} has shape {tuple(t.shape)}, the integer arguments say {tuple(shape)}")
-    return t
-
-
-def _ints(**kw):
-    for k, v in kw.items():
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise RuntimeError(f"{k} must be an int")
-        if v < 0 or v > 2147483647:
-            raise RuntimeError(f"{k} = {v} is out of range")
-
-
-def _call(name, tensors, *args):
-    dev = tensors[0].device
-    for t in tensors[1:]:
-        if t.device != dev:
-            raise RuntimeError("all tensors must be on one device")
-    fn = _fns.get(name)
-    if fn is None:
-        fn = _fns[name] = getattr(_lib.load(), name)
-    ptrs = iter(t.data_ptr() for t in tensors)
-    argv = [next(ptrs) if a is _P else a for a in args]
-    if dev.index == _torch.cuda.current_device():
-        rc = fn(*argv, _torch.cuda.current_stream().cuda_stream)
-    else:
-        with _torch.cuda.device(dev):
-            rc = fn(*argv, _torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        _lib.check(rc, name)
-    return 1
-
-
-_fns = {}
-_P = object()   # placeholder: the next tensor's device pointer
-_F, _I = _torch.float32, _torch.int32
+from ..._ext import _F, _I, _P, _call, _ints, _t
 
 
 def ball_query_wrapper(b, n, m, radius, nsample, new_xyz_tensor, xyz_tensor, idx_tensor):

@@ -16,8 +16,9 @@ code use it:
 Bound as ``sys.modules["pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"]`` (INTEGRATION.md,
 ``modest_amd.utils.pcdet_bind.install``).
 """
-from .pointnet2.pointnet2_batch.pointnet2_batch_cuda import _F, _I, _P, _call, _t, _torch
-from .roipoint_pool3d.roipoint_pool3d_cuda import _dims
+import torch as _torch
+
+from ._ext import _F, _I, _P, _call, _dims, _t
 
 
 def points_in_boxes_gpu(boxes_tensor, pts_tensor, box_idx_of_points_tensor):

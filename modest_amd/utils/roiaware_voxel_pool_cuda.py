@@ -19,9 +19,10 @@ Bound as ``sys.modules["pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"]`` by
 it unchanged.  ``modest_amd.utils.roiaware_pool3d_cuda`` -- what the default ``install()`` binds -- keeps answering
 ``NotImplementedError`` for ``forward`` / ``backward``.
 """
-from .pointnet2.pointnet2_batch.pointnet2_batch_cuda import _F, _I, _P, _call, _t, _torch
+import torch as _torch
+
+from ._ext import _F, _I, _P, _call, _dims, _t
 from .roiaware_pool3d_cuda import points_in_boxes_cpu, points_in_boxes_gpu  # noqa: F401  (re-exported)
-from .roipoint_pool3d.roipoint_pool3d_cuda import _dims
 
 
 def _method(pool_method):

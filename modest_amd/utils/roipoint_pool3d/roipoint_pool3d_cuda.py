@@ -3,22 +3,13 @@
 tensor arguments and return value 1, forwarded to ``modest_roipoint_pool3d`` of libmodest_hip.so
 on the current torch stream.  The reference asserts contiguity and takes every size from the
 tensors; here a tensor that is not a contiguous CUDA tensor of the expected dtype, or whose
-shape contradicts the others, raises ``RuntimeError``.
+shape contradicts the others, raises ``RuntimeError`` (``modest_amd/utils/_ext.py``).
 
 Bound as ``sys.modules["pcdet.ops.roipoint_pool3d.roipoint_pool3d_cuda"]`` (INTEGRATION.md,
 ``modest_amd.utils.pcdet_bind.install``), OpenPCDet's own ``roipoint_pool3d_utils.py`` runs on
 top of it unchanged.  What the op computes is DESIGN.md section 7e.
 """
-from ..pointnet2.pointnet2_batch.pointnet2_batch_cuda import _F, _I, _P, _call, _t, _torch
-
-
-def _dims(t, name, ndim, last):
-    if not isinstance(t, _torch.Tensor):
-        raise RuntimeError(f"{name} must be a tensor")
-    if t.dim() != ndim or (last is not None and t.shape[-1] != last):
-        raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected {ndim} dimensions"
-                           + (f" with the last one {last}" if last is not None else ""))
-    return tuple(t.shape)
+from .._ext import _F, _I, _P, _call, _dims, _t
 
 
 def forward(xyz, boxes3d, pts_feature, pooled_features, pooled_empty_flag):

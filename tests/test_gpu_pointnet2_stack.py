@@ -249,6 +249,69 @@ def test_query_nsample(ops, gpu, nsample):
         assert np.array_equal(got, seq.ball_query(radius, nsample, xyz, xcnt, cen, qcnt)), radius
 
 
+# ---- the batch layout and the stacked one run one walk and one three-NN core (csrc/pn2_search.h) -------------------------
+def layouts_case():
+    """B = 3 clouds of equal size on the seams of the shared code: 300 points (one whole 256-point step of the ball walk and
+    a partial one), 1100 known points (one whole tile of 1024 and 76 more, all in the first wavefront's quarter).  Centres
+    lie along rays out of the cloud, so their balls hold from many points down to none; some known points are repeated,
+    on both sides of the tile seam, and some unknown points sit right next to them: equal distances."""
+    rs = np.random.RandomState(5)
+    B, n, M, m, nu = 3, 300, 40, 1100, 70
+    xyz = rs.uniform(-1.5, 1.5, (B, n, 3)).astype(np.float32)
+    ray = rs.randn(B, M, 3)
+    ray /= np.linalg.norm(ray, axis=2, keepdims=True)
+    cen = (ray * np.linspace(0.0, 4.5, M)[None, :, None]).astype(np.float32)
+    known = rs.uniform(-1.5, 1.5, (B, m, 3)).astype(np.float32)
+    twins = ((3, 700), (1023, 1024), (5, 1090), (1030, 1099), (200, 201))
+    for a, b in twins:
+        known[:, b] = known[:, a]
+    unknown = rs.uniform(-1.5, 1.5, (B, nu, 3)).astype(np.float32)
+    for j, (a, _) in enumerate(twins):
+        unknown[:, j] = known[:, a] + np.float32(0.01) * rs.randn(B, 3).astype(np.float32)
+    return B, n, M, m, nu, xyz, cen, known, unknown
+
+
+def row_classes(idx):
+    """(no hit, short, full) of stacked ball-query rows over a prefill that no index equals: a row that was padded ends
+    in its first hit, a full one in a later point"""
+    hit = idx[:, 0] >= 0
+    return ~hit, hit & (idx[:, -1] == idx[:, 0]), hit & (idx[:, -1] != idx[:, 0])
+
+
+def test_the_two_layouts_agree(ops, gpu):
+    import pointnet2_seq as bseq
+    from modest_amd.utils.pointnet2.pointnet2_batch import pointnet2_batch_cuda as bops
+    B, n, M, m, nu, xyz, cen, known, unknown = layouts_case()
+    radius = 1.3                                        # about 100 of a cloud's 300 points around its middle
+    for ns in (5, 70):
+        given = (9000 + np.arange(B * M * ns)).reshape(B, M, ns).astype(I32)          # no index of a cloud
+        ref_b = bseq.ball_query(radius, ns, xyz, cen, given)
+        ref_s = seq.ball_query(radius, ns, xyz.reshape(-1, 3), (n,) * B, cen.reshape(-1, 3), (M,) * B, given.reshape(-1, ns))
+        none, short, full = row_classes(ref_s)
+        assert none.any() and short.any() and full.any(), (ns, none.sum(), short.sum(), full.sum())
+        got_b = dev(given, gpu)
+        assert bops.ball_query_wrapper(B, n, M, radius, ns, dev(cen, gpu), dev(xyz, gpu), got_b) == 1
+        got_b = got_b.cpu().numpy().reshape(-1, ns)
+        got_s = run_ball(ops, gpu, radius, ns, xyz.reshape(-1, 3), (n,) * B, cen.reshape(-1, 3), (M,) * B, given.reshape(-1, ns))
+        assert np.array_equal(got_b, ref_b.reshape(-1, ns)) and np.array_equal(got_s, ref_s), ns
+        assert np.array_equal(got_s[~none], got_b[~none]), ns                          # scan-local = the cloud's own
+        left = given.reshape(-1, ns)[none]
+        assert np.array_equal(got_b[none], left), ns
+        assert (got_s[none, 0] == -1).all() and np.array_equal(got_s[none, 1:], left[:, 1:]), ns
+    rd2_b, ri_b = bseq.three_nn(unknown, known)
+    rd2_s, ri_s = seq.three_nn(unknown.reshape(-1, 3), (nu,) * B, known.reshape(-1, 3), (m,) * B)
+    assert ((rd2_s[:, 0] == rd2_s[:, 1]) | (rd2_s[:, 1] == rd2_s[:, 2])).any()        # a tie the index order decides
+    d2_b = torch.full((B, nu, 3), -1.0, dtype=torch.float32, device=gpu)
+    i_b = torch.full((B, nu, 3), -1, dtype=torch.int32, device=gpu)
+    assert bops.three_nn_wrapper(B, nu, m, dev(unknown, gpu), dev(known, gpu), d2_b, i_b) == 1
+    d2_b, i_b = d2_b.cpu().numpy(), i_b.cpu().numpy()
+    d2_s, i_s = run_nn(ops, gpu, unknown.reshape(-1, 3), (nu,) * B, known.reshape(-1, 3), (m,) * B)
+    assert same_bits(d2_b, rd2_b) and np.array_equal(i_b, ri_b)
+    assert same_bits(d2_s, rd2_s) and np.array_equal(i_s, ri_s)
+    assert same_bits(d2_s, d2_b.reshape(-1, 3))
+    assert np.array_equal(i_s.reshape(B, nu, 3), i_b + (np.arange(B, dtype=I32) * m)[:, None, None])
+
+
 # ---- PV-RCNN's shapes, B = 2 -----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(ops, gpu):

@@ -217,11 +217,12 @@ def test_binding_is_opt_in():
 # ------------------------------------------------------------------------------------------------ the shim's checks
 def test_shim_raises_on_cpu_tensors_and_wrong_shapes_without_loading_the_library(monkeypatch):
     from modest_amd import _lib
+    from modest_amd.utils import _ext
 
     def no_load(*a, **k):
         raise AssertionError("the library was opened")
     monkeypatch.setattr(_lib, "load", no_load)
-    monkeypatch.setattr(ops, "_fns", {})
+    monkeypatch.setattr(_ext, "_fns", {})   # the binders' shared cache of entry points
     f, i = torch.float32, torch.int32
     xyz, new, cnt = torch.zeros((10, 3), dtype=f), torch.zeros((4, 3), dtype=f), torch.tensor([4], dtype=i)
     idx = torch.zeros((4, 8), dtype=i)
