@@ -1526,6 +1526,51 @@ int modest_pillar_scatter_backward(int64_t n_pillars, int channels, int batch, i
                                    const float *grad_canvas_dev, const void *coords_dev, int coord_code,
                                    float *grad_features_dev, void *stream);
 
+/* ---- a39: training-batch preparation (csrc/batch_prep.hip) ---------------------------------------------
+ * gt sampling (DataBaseSampler), random_world_flip / _rotation / _scaling, mask_points_and_boxes_outside_range and the near /
+ * far lists of sample_points for a whole batch; the arithmetic is stated at the top of csrc/batch_prep.hip.
+ * modest_batch_prep_stage1 BLOCKS: it ends with the call's one stream synchronise, after which table_pinned_host holds, per
+ * sample, modest_batch_prep_table_words() = 6 int32: points kept, far points, boxes kept, candidates kept, candidates dropped, 0.
+ * Tables (host copies are checked against every bound before anything is launched; the device copies must equal them):
+ *   samp (batch, 10) int64: first row of the sample in the virtual concatenation, object rows, first scene row, scene rows,
+ *     first box, gts, candidates, first candidate, first tile, 0 -- each "first" the running sum over the samples before;
+ *     a sample's tiles: ceil((object rows + scene rows) / modest_batch_prep_tile())
+ *   boxes (n_boxes, 12) float32: per sample its gts, then its candidates: x y z dx dy dz heading, cosf(h) sinf(h) cosf(-h)
+ *     sinf(-h) of the HOST's libm, the class index (0: a name outside class_names)
+ *   cand (n_cand, 3) int64: first row and rows in the database points, first object row within the sample;
+ *   cand_f64 (n_cand, 2): mv_height, the lowered box z (read with road_plane);  cand_group (n_cand) int32: equal numbers in a
+ *     run form a class group;  xf (batch, 8) float32: flip x, flip y (non-zero: drawn), cos, sin, float(angle), float(scale), 0, 0
+ *   ops_host: the augmentor steps in order, 1 flip x, 2 flip y, 3 rotation, 4 scaling;  range_host: x0 y0 z0 x1 y1 z1;
+ *   extra_width_host: REMOVE_EXTRA_WIDTH.
+ * Outputs: valid (n_cand) int32; points (n_rows, 1 + features), of which the first sum(points kept) rows are written: the
+ *   survivors of sample 0 in the concatenation's order, then sample 1's ..., column 0 the sample; lists (n_rows) int32: with
+ *   want_near, at the sample's first output row its near survivors' places among its survivors, in order, then its far ones';
+ *   gt_boxes (batch, gt_capacity, 8): the kept boxes with the class index, zeros behind them.
+ * modest_batch_prep_order only enqueues: out row i = the row that picks[i] = (4 sample + list, place) names -- list 0: the
+ *   sample's survivor `place`, 1 / 2: the survivor that entry `place` of its near / far list names -- read from the points, lists
+ *   and workspace a stage-1 call of the same n_rows and batch_size left.  perm (n_rows) int32 or NULL: shuffle_points ahead of
+ *   sample_points -- at the sample's first output row the order of its survivors (place i holds survivor perm[i]); places and
+ *   the near / far lists (rebuilt in lists2 (n_rows) int32 by one more launch) are then those of that order.
+ * Limits (the call fails and launches nothing): gts + candidates of a sample <= modest_batch_prep_max_boxes() = 512, 4 <= features
+ * <= 8, batch <= 65535, rows <= 2^31 - 1, a workspace of modest_batch_prep_workspace_bytes(n_rows, batch) (negative: a refusal).  */
+int modest_batch_prep_max_boxes(void);
+int modest_batch_prep_tile(void);
+int modest_batch_prep_table_words(void);
+int64_t modest_batch_prep_workspace_bytes(int64_t n_rows, int batch_size);
+int modest_batch_prep_stage1(int batch_size, int features, int64_t n_scene_rows, const float *scene_dev,
+                             int64_t n_db_rows, const float *db_dev, const int64_t *samp_host, const int64_t *samp_dev,
+                             int64_t n_boxes, const float *boxes_dev, int64_t n_cand, const int64_t *cand_host,
+                             const int64_t *cand_dev, const double *cand_f64_dev, const int32_t *cand_group_dev,
+                             const float *xf_dev, int n_ops, const int32_t *ops_host, const float *range_host,
+                             const float *extra_width_host, int road_plane, int want_near, int remove_outside_boxes,
+                             int min_num_corners, int64_t n_rows, int32_t *valid_dev, float *points_dev,
+                             int32_t *lists_dev, float *gt_boxes_dev, int gt_capacity, int32_t *table_pinned_host,
+                             void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_batch_prep_order(int batch_size, int features, int64_t n_rows, const float *points_dev,
+                            const int32_t *lists_dev, const void *workspace_dev, int64_t workspace_bytes,
+                            int64_t n_out, const int32_t *picks_dev, const int32_t *perm_dev, int32_t *lists2_dev,
+                            float *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,14 @@ SIGNATURES = {
                                              VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, C.c_int64, VP]),
     "modest_pillar_scatter": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP]),
     "modest_pillar_scatter_backward": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int, VP, VP]),
+    "modest_batch_prep_max_boxes": (C.c_int, []),
+    "modest_batch_prep_tile": (C.c_int, []),
+    "modest_batch_prep_table_words": (C.c_int, []),
+    "modest_batch_prep_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "modest_batch_prep_stage1": (C.c_int, [C.c_int, C.c_int, C.c_int64, VP, C.c_int64, VP, VP, VP, C.c_int64, VP, C.c_int64, VP,
+                                           VP, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                           VP, VP, VP, VP, C.c_int, VP, VP, C.c_int64, VP]),
+    "modest_batch_prep_order": (C.c_int, [C.c_int, C.c_int, C.c_int64, VP, VP, VP, C.c_int64, C.c_int64, VP, VP, VP, VP, VP]),
 }
 
 _lib = None

@@ -2573,3 +2573,323 @@ def pillar_scatter_backward(grad_canvas: torch.Tensor, coords: torch.Tensor, *, 
                                                     _PILLAR_CODES[coords.dtype], _ptr_filled(grad), _stream()),
               "modest_pillar_scatter_backward")
     return grad
+
+
+# --------------------------------------------------------------------------- training-batch preparation
+BATCH_PREP_STEPS = {"flip_x": 1, "flip_y": 2, "rotation": 3, "scaling": 4}
+BATCH_PREP_MAX_BATCH = 65535
+BATCH_PREP_TABLE = ("points", "far", "boxes", "candidates_kept", "candidates_dropped")
+_BP_SAMP_COLS = 10
+
+
+def batch_prep_max_boxes() -> int:
+    """gts plus candidates of a sample the box workgroup stages in LDS"""
+    return int(load().modest_batch_prep_max_boxes())
+
+
+def batch_prep_tile() -> int:
+    """rows of a points workgroup; a tile never spans two samples"""
+    return int(load().modest_batch_prep_tile())
+
+
+def batch_prep_workspace_bytes(n_rows: int, batch_size: int) -> int:
+    return _workspace_bytes("modest_batch_prep_workspace_bytes", n_rows, batch_size)
+
+
+def _host_trig4(h: np.ndarray) -> np.ndarray:
+    """(n, 4) float32 cosf(h), sinf(h), cosf(-h), sinf(-h) of the host's C library (kitti_infos.host_cos_sin_f32)"""
+    from .kitti_infos import host_cos_sin_f32
+    h = np.asarray(h, np.float32).ravel()
+    cp, sp = host_cos_sin_f32(-h)
+    cn, sn = host_cos_sin_f32(h)
+    return np.stack([cp, sp, cn, sn], axis=1).astype(np.float32).reshape(-1, 4)
+
+
+class BatchPrepPlan:
+    """the host tables of a batch (include/modest_hip.h, a39) and their totals"""
+    __slots__ = ("B", "F", "steps", "road_plane", "samp", "boxes", "cand", "cand_f64", "cand_group", "xf", "n_rows", "n_scene",
+                 "n_boxes", "n_cand", "gt_capacity")
+
+
+def _bp_boxes(a, name, b):
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 2 and a.size == 0:
+        a = a.reshape(0, 7)
+    if a.ndim != 2 or a.shape[1] < 7:
+        raise ValueError(f"sample {b}: {name} {a.shape} must be (n, 7)")
+    if a.shape[1] > 7:
+        raise NotImplementedError(f"sample {b}: {name} has {a.shape[1]} columns: boxes with more than 7 columns (the velocity "
+                                  f"columns) are not provided")
+    return a
+
+
+def batch_prep_plan(samples, db_offsets, features: int, steps=(), road_plane: bool = False) -> BatchPrepPlan:
+    """The host half of stage 1: numpy only, no device data.  samples: per sample a dict with n_points (its scene rows, stacked
+    in sample order), gt_boxes (G, 7), gt_classes (G,) (0: a name outside class_names), cand_boxes (C, 7), cand_classes (C,),
+    cand_groups (C,) (a run of equal numbers is a class group, in the sampler's order), cand_objects (C,) rows of db_offsets,
+    with road_plane mv_height (C,) float64 and cand_z (C,) the lowered z, and the draws: flip_x, flip_y, cos, sin, angle, scale
+    (each read only if its step is in `steps`, names of BATCH_PREP_STEPS in the augmentors' order, each at most once).
+    db_offsets (objects + 1,) int64: the objects' first rows in the packed database points."""
+    steps = [str(s) for s in steps]
+    for s in steps:
+        if s not in BATCH_PREP_STEPS:
+            raise NotImplementedError(f"augmentor step {s!r} is not provided: {sorted(BATCH_PREP_STEPS)}")
+    if len(set(steps)) != len(steps):
+        raise NotImplementedError(f"augmentor steps {steps}: a step that occurs twice is not provided")
+    F, B = int(features), len(samples)
+    if not 4 <= F <= 8:
+        raise ValueError(f"features = {F}: 4 to 8 point features")
+    if B > BATCH_PREP_MAX_BATCH:
+        raise ValueError(f"batch of {B} samples is above the limit of {BATCH_PREP_MAX_BATCH}")
+    off = np.asarray(db_offsets, dtype=np.int64).ravel()
+    if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("db_offsets must start at 0 and never fall")
+    limit, tile = batch_prep_max_boxes(), batch_prep_tile()
+    pl = BatchPrepPlan()
+    pl.B, pl.F, pl.steps, pl.road_plane = B, F, np.array([BATCH_PREP_STEPS[s] for s in steps], np.int32), bool(road_plane)
+    samp = np.zeros((B, _BP_SAMP_COLS), np.int64)
+    xf = np.zeros((B, 8), np.float32)
+    boxes, cands, cf64, groups = [], [], [], []
+    vrow = scene = nbox = ncand = ntile = 0
+    for b, s in enumerate(samples):
+        gt = _bp_boxes(s["gt_boxes"], "gt_boxes", b)
+        cb = _bp_boxes(s.get("cand_boxes", np.zeros((0, 7), np.float32)), "cand_boxes", b)
+        G, Cn = len(gt), len(cb)
+        if G + Cn > limit:
+            raise ValueError(f"sample {b}: {G} gts plus {Cn} candidates are above the limit of {limit} boxes")
+        gcls = np.asarray(s["gt_classes"], np.int64).ravel()
+        ccls = np.asarray(s.get("cand_classes", np.zeros(0)), np.int64).ravel()
+        grp = np.asarray(s.get("cand_groups", np.zeros(0)), np.int64).ravel()
+        objs = np.asarray(s.get("cand_objects", np.zeros(0)), np.int64).ravel()
+        if len(gcls) != G or len(ccls) != Cn or len(grp) != Cn or len(objs) != Cn:
+            raise ValueError(f"sample {b}: gt_classes, cand_classes, cand_groups and cand_objects must have a number per box")
+        if Cn and (objs.min() < 0 or objs.max() >= off.size - 1):
+            raise ValueError(f"sample {b}: cand_objects outside the database's {off.size - 1} objects")
+        n = int(s["n_points"])
+        if n < 0:
+            raise ValueError(f"sample {b}: n_points = {n}")
+        cnt = off[objs + 1] - off[objs] if Cn else np.zeros(0, np.int64)
+        first = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        nobj = int(first[-1])
+        samp[b] = (vrow, nobj, scene, n, nbox, G, Cn, ncand, ntile, 0)
+        allb = np.concatenate([gt, cb], axis=0)
+        row = np.zeros((G + Cn, 12), np.float32)
+        row[:, :7] = allb
+        row[:, 7:11] = _host_trig4(allb[:, 6])
+        row[:, 11] = np.concatenate([gcls, ccls]).astype(np.float32)
+        boxes.append(row)
+        cands.append(np.stack([off[objs] if Cn else cnt, cnt, first[:-1]], axis=1).astype(np.int64).reshape(-1, 3))
+        f64 = np.zeros((Cn, 2), np.float64)
+        if road_plane and Cn:
+            mv, cz = np.asarray(s["mv_height"], np.float64).ravel(), np.asarray(s["cand_z"], np.float32).ravel()
+            if len(mv) != Cn or len(cz) != Cn:
+                raise ValueError(f"sample {b}: mv_height and cand_z must have a number per candidate")
+            f64[:, 0], f64[:, 1] = mv, cz.astype(np.float64)
+        cf64.append(f64)
+        groups.append(grp.astype(np.int32))
+        if "flip_x" in steps:
+            xf[b, 0] = 1.0 if s["flip_x"] else 0.0
+        if "flip_y" in steps:
+            xf[b, 1] = 1.0 if s["flip_y"] else 0.0
+        if "rotation" in steps:
+            xf[b, 2], xf[b, 3], xf[b, 4] = np.float32(s["cos"]), np.float32(s["sin"]), np.float32(s["angle"])
+        if "scaling" in steps:
+            xf[b, 5] = np.float32(s["scale"])
+        vrow += nobj + n
+        scene += n
+        nbox += G + Cn
+        ncand += Cn
+        ntile += (nobj + n + tile - 1) // tile
+    if vrow > 2 ** 31 - 1:
+        raise ValueError(f"{vrow} rows in a call are above the limit of 2^31 - 1")
+    pl.samp, pl.xf = samp, xf
+    pl.boxes = np.concatenate(boxes, axis=0) if boxes else np.zeros((0, 12), np.float32)
+    pl.cand = np.concatenate(cands, axis=0) if cands else np.zeros((0, 3), np.int64)
+    pl.cand_f64 = np.concatenate(cf64, axis=0) if cf64 else np.zeros((0, 2), np.float64)
+    pl.cand_group = np.concatenate(groups) if groups else np.zeros((0,), np.int32)
+    pl.n_rows, pl.n_scene, pl.n_boxes, pl.n_cand = vrow, scene, nbox, ncand
+    pl.gt_capacity = int((samp[:, 5] + samp[:, 6]).max()) if B else 0
+    return pl
+
+
+class BatchPrepStage1:
+    """what a stage-1 call leaves: the buffers stage 2 reads, and the pinned table's counts (numpy, the call's own)"""
+    __slots__ = ("B", "F", "n_rows", "points", "lists", "gt_boxes", "valid", "table", "table_pinned", "workspace", "want_near")
+
+    def counts(self, name: str) -> np.ndarray:
+        return self.table[:, BATCH_PREP_TABLE.index(name)]
+
+
+def _bp_upload(arrays, staging, dev):
+    """the arrays packed 8-byte aligned into one pinned buffer and copied to the device in one asynchronous copy
+    -> (device views, staging)"""
+    sizes = [(a.nbytes + 7) // 8 * 8 for a in arrays]
+    total = max(sum(sizes), 8)
+    if staging is None or staging.numel() < total:
+        staging = torch.empty((max(total, 4096),), dtype=torch.uint8).pin_memory()
+    if not staging.is_pinned() or staging.dtype != torch.uint8:
+        raise ValueError("staging must be a pinned uint8 tensor")
+    host = staging.numpy()
+    o = 0
+    for a, sz in zip(arrays, sizes):
+        host[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).ravel()
+        o += sz
+    dev_buf = staging[:total].to(dev, non_blocking=True)
+    views, o = [], 0
+    for a, sz in zip(arrays, sizes):
+        views.append(dev_buf[o:o + a.nbytes])
+        o += sz
+    return views, staging
+
+
+def batch_prep_stage1(plan: BatchPrepPlan, scene_points: torch.Tensor, db_points: torch.Tensor, point_cloud_range, *,
+                      remove_extra_width=(0.0, 0.0, 0.0), want_near: bool = False, remove_outside_boxes: bool = True,
+                      min_num_corners: int = 1, workspace: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None,
+                      staging: Optional[torch.Tensor] = None, out=None):
+    """modest_batch_prep_stage1 on PyTorch's current stream: BLOCKING (one synchronise, inside the library).
+    scene_points (plan.n_scene, F) float32: the raw scans stacked in sample order; db_points (rows, F) float32: the packed
+    database objects.  The candidates that collide are dropped, the kept ones' object rows and the scene rows outside their
+    enlarged boxes go through the plan's augmentor steps and the x / y range mask, stably compacted; the boxes go through the
+    same steps, limit_period, the class filter and (remove_outside_boxes) the corner mask.
+    -> (BatchPrepStage1, staging): points (n_rows, 1 + F) of which the first table[:, 0].sum() rows are written, stacked with the
+    sample in column 0; gt_boxes (B, plan.gt_capacity, 8) zero-padded; valid (n_cand,) int32; table (B, 5) int32 of
+    BATCH_PREP_TABLE.  workspace, table (pinned int32), staging (pinned uint8): reused when large enough, else allocated."""
+    if not isinstance(plan, BatchPrepPlan):
+        raise ValueError("plan must be a BatchPrepPlan (ops.batch_prep_plan)")
+    dev = _device_tensors((("scene_points", scene_points), ("db_points", db_points)), same_device=True)
+    B, F = plan.B, plan.F
+    for name, t, rows in (("scene_points", scene_points, plan.n_scene), ("db_points", db_points, None)):
+        if t.ndim != 2 or int(t.shape[1]) != F or (rows is not None and int(t.shape[0]) != rows) or not t.is_contiguous():
+            raise ValueError(f"{name} {tuple(t.shape)} must be a contiguous ({'rows' if rows is None else rows}, {F}) tensor")
+    rng = np.ascontiguousarray(np.asarray(point_cloud_range, dtype=np.float32).ravel())
+    extra = np.ascontiguousarray(np.asarray(remove_extra_width, dtype=np.float32).ravel())
+    if rng.size != 6 or extra.size != 3:
+        raise ValueError("point_cloud_range must hold 6 numbers and remove_extra_width 3")
+    if int(min_num_corners) < 0 or int(min_num_corners) > 8:
+        raise ValueError(f"min_num_corners = {min_num_corners} is outside 0 .. 8")
+    n, G = plan.n_rows, plan.gt_capacity
+    points, lists, gt, valid = _outputs((("points", torch.float32, (n, 1 + F), True), ("lists", torch.int32, (n,), True),
+                                         ("gt_boxes", torch.float32, (B, G, 8), True),
+                                         ("valid", torch.int32, (plan.n_cand,), True)), out, dev)
+    workspace = _workspace(batch_prep_workspace_bytes(n, B), workspace, dev)
+    words = B * 6
+    if table is None or table.numel() < words:
+        table = torch.zeros((max(words, 16),), dtype=torch.int32).pin_memory()
+    if not table.is_pinned() or table.dtype != torch.int32 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous pinned int32 tensor")
+    st = BatchPrepStage1()
+    st.B, st.F, st.n_rows, st.points, st.lists, st.gt_boxes, st.valid = B, F, n, points, lists, gt, valid
+    st.workspace, st.want_near, st.table_pinned = workspace, bool(want_near), table
+    if B == 0:
+        st.table = np.zeros((0, 5), np.int32)
+        return st, staging
+    (samp_d, boxes_d, cand_d, f64_d, grp_d, xf_d), staging = _bp_upload(
+        [plan.samp, plan.boxes, plan.cand, plan.cand_f64, plan.cand_group, plan.xf], staging, dev)
+    ptr = _ptr_filled
+    with torch.cuda.device(dev):
+        check(load().modest_batch_prep_stage1(
+            B, F, plan.n_scene, ptr(scene_points), int(db_points.shape[0]), ptr(db_points), _np_ptr(plan.samp), samp_d.data_ptr(),
+            plan.n_boxes, ptr(boxes_d), plan.n_cand, _np_ptr(plan.cand) if plan.n_cand else None, ptr(cand_d), ptr(f64_d),
+            ptr(grp_d), xf_d.data_ptr(), len(plan.steps), _np_ptr(plan.steps) if len(plan.steps) else None, _np_ptr(rng),
+            _np_ptr(extra), int(plan.road_plane), int(bool(want_near)), int(bool(remove_outside_boxes)), int(min_num_corners), n,
+            ptr(valid), ptr(points), ptr(lists), ptr(gt), G, table.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            _stream()), "modest_batch_prep_stage1")
+    st.table = table[:words].view(B, 6).numpy()[:, :5].copy()
+    return st, staging
+
+
+def batch_prep_order_draws(table: np.ndarray, num_points: Optional[int] = None, shuffle: bool = False, np_random=None,
+                           shuffle_first: bool = False):
+    """Stage 2 on the host, from the counts alone: for samples 0 .. B - 1 the reference's draws of sample_points
+    (data_processor.py:82-118; num_points None: not configured) and then of shuffle_points (shuffle), on `np_random` (None: the
+    global np.random).  choice(array, k, replace=False) is array[permutation(len)[:k]], so positions are drawn as positions.
+    shuffle_first: shuffle_points stands AHEAD of sample_points in the config: per sample its permutation is drawn first, and
+    the places and lists of the picks are those of the shuffled sample (the device rebuilds its near / far lists from the
+    permutation, ops.batch_prep_order).
+    -> (picks (n_out, 2) int32 of (4 sample + list, place), list 0 the survivors, 1 the near list, 2 the far list; rows per
+    sample (B,) int64), and with shuffle_first a third entry: perm (sum of the points kept,) int32, the samples' permutations
+    stacked"""
+    npr = np.random if np_random is None else np_random
+    table = np.asarray(table)
+    picks, rows, perms = [], [], []
+    for b in range(len(table)):
+        k, far = int(table[b, 0]), int(table[b, 1])
+        lid, pos = np.zeros(k, np.int64), np.arange(k, dtype=np.int64)
+        if shuffle_first:
+            perms.append(np.asarray(npr.permutation(k), np.int32) if shuffle else np.arange(k, dtype=np.int32))
+        if num_points is not None and int(num_points) != -1:
+            m = int(num_points)
+            if k == 0 and m > 0:
+                raise ValueError(f"sample {b}: sample_points on a sample without points (the reference does not end)")
+            if m < k:
+                if m > far:
+                    sel = npr.permutation(k - far)[:m - far]
+                    lid = np.concatenate([np.full(len(sel), 1, np.int64), np.full(far, 2, np.int64)])
+                    pos = np.concatenate([np.asarray(sel, np.int64), np.arange(far, dtype=np.int64)])
+                else:
+                    pos = np.asarray(npr.permutation(k)[:m], np.int64)
+                    lid = np.zeros(m, np.int64)
+            else:
+                while m > len(pos):
+                    pos = np.concatenate([pos, np.asarray(npr.permutation(k)[:min(k, m - len(pos))], np.int64)])
+                lid = np.zeros(len(pos), np.int64)
+            order = np.arange(len(pos))
+            npr.shuffle(order)
+            lid, pos = lid[order], pos[order]
+        if shuffle and not shuffle_first:
+            order = npr.permutation(len(pos))
+            lid, pos = lid[order], pos[order]
+        picks.append(np.stack([4 * b + lid, pos], axis=1))
+        rows.append(len(pos))
+    out = np.concatenate(picks, axis=0).astype(np.int32) if picks else np.zeros((0, 2), np.int32)
+    if shuffle_first:
+        return out, np.asarray(rows, np.int64), (np.concatenate(perms) if perms else np.zeros(0, np.int32))
+    return out, np.asarray(rows, np.int64)
+
+
+def batch_prep_order(st: BatchPrepStage1, picks: np.ndarray, *, perm: Optional[np.ndarray] = None,
+                     staging: Optional[torch.Tensor] = None, out=None):
+    """modest_batch_prep_order on PyTorch's current stream: enqueue only.  picks (n_out, 2) int32 (batch_prep_order_draws),
+    checked against the stage-1 table before the launch.  perm: the third entry of batch_prep_order_draws(shuffle_first=True),
+    checked to hold, per sample, places of its survivors only; one more launch then rebuilds the near / far lists in the
+    shuffled order.  -> (points (n_out, 1 + F) float32, staging)"""
+    if not isinstance(st, BatchPrepStage1):
+        raise ValueError("st must be the BatchPrepStage1 of ops.batch_prep_stage1")
+    picks = np.ascontiguousarray(picks)
+    if picks.dtype != np.int32 or picks.ndim != 2 or picks.shape[1] != 2:
+        raise ValueError(f"picks {picks.shape} {picks.dtype} must be (n_out, 2) int32")
+    n_out = len(picks)
+    if n_out > 2 ** 31 - 1:
+        raise ValueError(f"{n_out} rows in a call are above the limit of 2^31 - 1")
+    if n_out:
+        b, lid, pos = picks[:, 0] >> 2, picks[:, 0] & 3, picks[:, 1]
+        if b.min() < 0 or b.max() >= st.B or lid.max() > 2 or pos.min() < 0:
+            raise ValueError("picks name a sample or a list that does not exist")
+        if lid.any() and not st.want_near:
+            raise ValueError("picks name the near / far lists of a stage 1 run without want_near")
+        kept, far = st.table[b, 0], st.table[b, 1]
+        if (pos >= np.where(lid == 0, kept, np.where(lid == 1, kept - far, far))).any():
+            raise ValueError("picks name a place behind the end of its list")
+    dev = st.points.device
+    if perm is not None:
+        perm = np.ascontiguousarray(perm)
+        kept = st.table[:, 0].astype(np.int64)
+        if perm.dtype != np.int32 or perm.ndim != 1 or len(perm) != int(kept.sum()):
+            raise ValueError(f"perm {perm.shape} {perm.dtype} must be ({int(kept.sum())},) int32: a place per point kept")
+        if len(perm) and ((perm < 0) | (perm >= np.repeat(kept, kept))).any():
+            raise ValueError("perm names a survivor its sample does not have")
+    (res,) = _outputs((("points", torch.float32, (n_out, 1 + st.F), True),), None if out is None else (out,), dev)
+    if n_out == 0:
+        return res, staging
+    if perm is not None:
+        (picks_d, perm_d), staging = _bp_upload([picks, perm], staging, dev)
+        lists2 = torch.empty((max(st.n_rows, 1),), dtype=torch.int32, device=dev)
+    else:
+        (picks_d,), staging = _bp_upload([picks], staging, dev)
+        perm_d = lists2 = None
+    with torch.cuda.device(dev):
+        check(load().modest_batch_prep_order(st.B, st.F, st.n_rows, _ptr_filled(st.points), _ptr_filled(st.lists),
+                                             st.workspace.data_ptr(), st.workspace.numel(), n_out, picks_d.data_ptr(),
+                                             _ptr_filled(perm_d), _ptr(lists2), res.data_ptr(), _stream()),
+              "modest_batch_prep_order")
+    return res, staging

@@ -124,6 +124,9 @@ BOX_DECODE = "modest_amd.utils.box_decode"             # its methods set on the 
 PILLAR_VFE_NAMES = {"pcdet.models.backbones_3d.vfe.pillar_vfe": "PillarVFE",
                     "pcdet.models.backbones_2d.map_to_bev.pointpillar_scatter": "PointPillarScatter"}
 PILLAR_VFE = "modest_amd.utils.pillar_vfe"             # its two forward methods set on the two classes by bind_pillar_vfe()
+BATCH_PREP_DATASET_NAME = "pcdet.datasets.dataset"
+BATCH_PREP_MODELS_NAME = "pcdet.models"
+BATCH_PREP = "modest_amd.utils.batch_prep"             # prepare_data, collate_batch and load_data_to_gpu set by bind_batch_prep()
 
 
 class StandIn(types.ModuleType):
@@ -294,6 +297,27 @@ def bind_pillar_vfe():
     forward keeps its own; parameters and buffers are untouched.  A module that lacks its class is skipped.  Idempotent; before
     or after ``import pcdet.models``; touches no GPU state."""
     return _bind_onto_each(PILLAR_VFE_NAMES, PILLAR_VFE, with_class_name=True)
+
+
+def bind_batch_prep():
+    """DatasetTemplate.prepare_data / .collate_batch and pcdet.models.load_data_to_gpu := the three functions of
+    modest_amd.utils.batch_prep -- training-batch preparation on the device -- in the reference's modules
+    if they are imported or can be -> (pcdet.datasets.dataset, pcdet.models), or None where either cannot be imported.  A
+    function of its own, opt-in: install() and what it returns stay as they are.  In test mode, and for a batch that is not
+    raw, the three call what they replaced.  Idempotent; touches no GPU state (the database is read at the first raw batch)."""
+    mods = []
+    for name in (BATCH_PREP_DATASET_NAME, BATCH_PREP_MODELS_NAME):
+        mod = sys.modules.get(name)
+        if mod is None:
+            try:
+                mod = importlib.import_module(name)
+            except ImportError:
+                return None
+        mods.append(mod)
+    if getattr(mods[0], "DatasetTemplate", None) is None or getattr(mods[1], "load_data_to_gpu", None) is None:
+        return None
+    importlib.import_module(BATCH_PREP).bind(mods[0].DatasetTemplate, mods[1])
+    return tuple(mods)
 
 
 def install(stand_ins=True, sparse_conv=False, point_stack=False, anchor_targets=False, roiaware_pool=False,
