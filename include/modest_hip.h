@@ -1571,6 +1571,40 @@ int modest_batch_prep_order(int batch_size, int features, int64_t n_rows, const 
                             int64_t n_out, const int32_t *picks_dev, const int32_t *perm_dev, int32_t *lists2_dev,
                             float *out_dev, void *stream);
 
+/* ---- a40: the optimiser step (csrc/optim_step.hip) -------------------------------------------------------
+ * clip_grad_norm_ and OptimWrapper.step (decoupled weight decay + torch.optim.Adam.step) over one table of the whole parameter
+ * set; the arithmetic and the summation order are stated at the top of csrc/optim_step.hip.  Every call only enqueues on
+ * `stream`; it waits for the device only where the host has run a whole ring of the context's pinned staging slots ahead.
+ * Tables (host copies; every bound is checked on them before anything is launched), one record per tensor, none without elements:
+ *   static (n_tensors, 40 bytes): uint64 p, m, v (device addresses, 4-byte aligned; m and v may be 0 on a tensor without a
+ *     gradient, all three where the call reads no state), int64 n, int32 first chunk (the running sum of ceil(n /
+ *     modest_optim_chunk())), int32 0.  Copied to the workspace only with upload_static: pass 0 while the workspace holds a copy
+ *     of the same table.
+ *   step (n_tensors, 48 bytes): uint64 g (0: no gradient this step), float32 dec, w, omw = 1 - w, b2, omb2, bc2s, eps, nss,
+ *     uint32 flags (1: w >= 0.5, the other branch of lerp), int32 norm_first (the running sum of the chunks of the tensors with
+ *     a gradient; -1 without one).
+ * modest_optim_grad_norm: *norm_out_dev = (float) sqrt(sum g^2).  modest_optim_clip: that, then g *= coef in place.
+ * modest_optim_step: the step with the gradients as they are.  modest_optim_norm_step: the norm, then the step on fl(g * coef);
+ * the gradients are not written.  n_chunks: the sum of the tensors' chunks.  finish_launch 0: every workgroup of the consumer
+ * sums the chunk partials itself (two launches); non-zero: a one-workgroup launch between the two sums them once and the
+ * consumer reads the coefficient it left (three launches) -- the same bits either way.
+ * Limits (the call fails and launches nothing): 1 <= n_tensors <= 2^20, n_chunks <= 2^31 - 1, a 256-byte aligned workspace of
+ * modest_optim_workspace_bytes(n_tensors, n_chunks) bytes (negative: a refusal).                                                 */
+int modest_optim_chunk(void);
+int64_t modest_optim_workspace_bytes(int64_t n_tensors, int64_t n_chunks);
+int modest_optim_grad_norm(modest_ctx *ctx, int64_t n_tensors, int64_t n_chunks, const void *static_host,
+                           const void *step_host, int upload_static, float *norm_out_dev, void *workspace_dev,
+                           int64_t workspace_bytes, void *stream);
+int modest_optim_clip(modest_ctx *ctx, int64_t n_tensors, int64_t n_chunks, const void *static_host,
+                      const void *step_host, int upload_static, float max_norm, int finish_launch,
+                      float *norm_out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+int modest_optim_step(modest_ctx *ctx, int64_t n_tensors, int64_t n_chunks, const void *static_host,
+                      const void *step_host, int upload_static, void *workspace_dev, int64_t workspace_bytes,
+                      void *stream);
+int modest_optim_norm_step(modest_ctx *ctx, int64_t n_tensors, int64_t n_chunks, const void *static_host,
+                           const void *step_host, int upload_static, float max_norm, int finish_launch,
+                           float *norm_out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,12 @@ SIGNATURES = {
                                            VP, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                            VP, VP, VP, VP, C.c_int, VP, VP, C.c_int64, VP]),
     "modest_batch_prep_order": (C.c_int, [C.c_int, C.c_int, C.c_int64, VP, VP, VP, C.c_int64, C.c_int64, VP, VP, VP, VP, VP]),
+    "modest_optim_chunk": (C.c_int, []),
+    "modest_optim_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "modest_optim_grad_norm": (C.c_int, [VP, C.c_int64, C.c_int64, VP, VP, C.c_int, VP, VP, C.c_int64, VP]),
+    "modest_optim_clip": (C.c_int, [VP, C.c_int64, C.c_int64, VP, VP, C.c_int, C.c_float, C.c_int, VP, VP, C.c_int64, VP]),
+    "modest_optim_step": (C.c_int, [VP, C.c_int64, C.c_int64, VP, VP, C.c_int, VP, C.c_int64, VP]),
+    "modest_optim_norm_step": (C.c_int, [VP, C.c_int64, C.c_int64, VP, VP, C.c_int, C.c_float, C.c_int, VP, VP, C.c_int64, VP]),
 }
 
 _lib = None

@@ -2893,3 +2893,81 @@ def batch_prep_order(st: BatchPrepStage1, picks: np.ndarray, *, perm: Optional[n
                                              _ptr_filled(perm_d), _ptr(lists2), res.data_ptr(), _stream()),
               "modest_batch_prep_order")
     return res, staging
+
+
+# --------------------------------------------------------------------------- the optimiser step
+OPTIM_STATIC = np.dtype([("p", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("first_chunk", "<i4"), ("pad", "<i4")])
+OPTIM_STEP = np.dtype([("g", "<u8"), ("dec", "<f4"), ("w", "<f4"), ("omw", "<f4"), ("b2", "<f4"), ("omb2", "<f4"), ("bc2s", "<f4"),
+                       ("eps", "<f4"), ("nss", "<f4"), ("flags", "<u4"), ("norm_first", "<i4")])
+OPTIM_LERP_HIGH = 1
+_optim_chunk = None
+
+
+def optim_chunk() -> int:
+    """elements of a chunk: a tensor of n elements owns ceil(n / optim_chunk()) chunks"""
+    global _optim_chunk
+    if _optim_chunk is None:
+        _optim_chunk = int(load().modest_optim_chunk())
+    return _optim_chunk
+
+
+def optim_workspace_bytes(n_tensors: int, n_chunks: int) -> int:
+    return _workspace_bytes("modest_optim_workspace_bytes", n_tensors, n_chunks)
+
+
+def _optim_call(fn_name, static, step, upload_static, workspace, middle, ctx):
+    """what the four optimiser calls share: the two host tables (structured arrays of OPTIM_STATIC / OPTIM_STEP, one record per
+    tensor), the workspace, PyTorch's current stream"""
+    if not isinstance(static, np.ndarray) or static.dtype != OPTIM_STATIC or static.ndim != 1 or not static.flags.c_contiguous:
+        raise TypeError("static must be a contiguous 1-d array of ops.OPTIM_STATIC")
+    if not isinstance(step, np.ndarray) or step.dtype != OPTIM_STEP or step.shape != static.shape or not step.flags.c_contiguous:
+        raise TypeError("step must be a contiguous array of ops.OPTIM_STEP with one record per record of static")
+    T = int(static.shape[0])
+    if T < 1:
+        raise ValueError("the table holds no tensor")
+    n_chunks = int(static["first_chunk"][-1]) + -(-int(static["n"][-1]) // optim_chunk())
+    _dev(workspace, torch.uint8, "workspace")
+    nb = optim_workspace_bytes(T, n_chunks)
+    if workspace.numel() < nb:
+        raise ValueError(f"workspace holds {workspace.numel()} bytes, {nb} are needed")
+    for name, t in middle:
+        if isinstance(t, (float, int)):
+            continue
+        if _dev(t, torch.float32, name).numel() != 1 or t.device != workspace.device:
+            raise ValueError(f"{name} must be one float32 on {workspace.device}")
+    ctx = _ctx(ctx, workspace)
+    args = [a.data_ptr() if torch.is_tensor(a) else a for _, a in middle]
+    with torch.cuda.device(workspace.device):
+        check(getattr(load(), fn_name)(ctx.handle, T, n_chunks, _np_ptr(static), _np_ptr(step), 1 if upload_static else 0, *args,
+                                       workspace.data_ptr(), workspace.numel(), _stream()), fn_name)
+
+
+def optim_grad_norm(static, step, workspace: torch.Tensor, norm_out: torch.Tensor, *, upload_static: bool = True,
+                    ctx: Optional[Context] = None) -> torch.Tensor:
+    """modest_optim_grad_norm on PyTorch's current stream: enqueue only.  -> norm_out (one float32 on the device) :=
+    (float) sqrt(sum g^2) over the gradients the step table names."""
+    _optim_call("modest_optim_grad_norm", static, step, upload_static, workspace, (("norm_out", norm_out),), ctx)
+    return norm_out
+
+
+def optim_clip(static, step, max_norm: float, workspace: torch.Tensor, norm_out: torch.Tensor, *, upload_static: bool = True,
+               finish_launch: bool = False, ctx: Optional[Context] = None) -> torch.Tensor:
+    """modest_optim_clip: the norm as optim_grad_norm leaves it, then every gradient *= coef in place (two launches; three with
+    finish_launch, where one workgroup sums the chunk partials once instead of every workgroup of the clip: the same bits)."""
+    _optim_call("modest_optim_clip", static, step, upload_static, workspace,
+                (("max_norm", float(max_norm)), ("finish_launch", int(bool(finish_launch))), ("norm_out", norm_out)), ctx)
+    return norm_out
+
+
+def optim_step(static, step, workspace: torch.Tensor, *, upload_static: bool = True, ctx: Optional[Context] = None) -> None:
+    """modest_optim_step: decay and Adam update of every tensor of the table in one launch, the gradients as they are."""
+    _optim_call("modest_optim_step", static, step, upload_static, workspace, (), ctx)
+
+
+def optim_norm_step(static, step, max_norm: float, workspace: torch.Tensor, norm_out: torch.Tensor, *, upload_static: bool = True,
+                    finish_launch: bool = False, ctx: Optional[Context] = None) -> torch.Tensor:
+    """modest_optim_norm_step: the norm, then the step on fl(g * coef) (two launches; three with finish_launch, as in optim_clip);
+    the gradients are not written."""
+    _optim_call("modest_optim_norm_step", static, step, upload_static, workspace,
+                (("max_norm", float(max_norm)), ("finish_launch", int(bool(finish_launch))), ("norm_out", norm_out)), ctx)
+    return norm_out

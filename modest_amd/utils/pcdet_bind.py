@@ -76,6 +76,12 @@ PointPillars' feature encoder and BEV scatter with their fused backward (DESIGN.
 ``pcdet.models.backbones_3d.vfe.pillar_vfe`` and ``PointPillarScatter`` of
 ``pcdet.models.backbones_2d.map_to_bev.pointpillar_scatter``, whose modules are imported for it if they are not yet; a subclass
 that overrides ``forward`` keeps its own.  Parameters, buffers and ``state_dict`` stay the modules' own.
+
+``bind_optim_step()``, a function of its own like the others, sets ``step`` and ``clip_and_step`` of
+``modest_amd.utils.optim_step`` -- the ``adam_onecycle`` optimiser step: ``step`` is one launch, the bound pair of
+``clip_grad_norm_`` and ``step`` three -- on ``OptimWrapper`` of
+``train_utils.optimization.fastai_optim`` and its ``clip_grad_norm_`` as that name in ``train_utils.train_utils``; both modules
+import only with the reference's ``tools/`` on ``sys.path``.  The optimiser's state stays torch's own.
 """
 import importlib
 import importlib.util
@@ -127,6 +133,9 @@ PILLAR_VFE = "modest_amd.utils.pillar_vfe"             # its two forward methods
 BATCH_PREP_DATASET_NAME = "pcdet.datasets.dataset"
 BATCH_PREP_MODELS_NAME = "pcdet.models"
 BATCH_PREP = "modest_amd.utils.batch_prep"             # prepare_data, collate_batch and load_data_to_gpu set by bind_batch_prep()
+OPTIM_STEP_WRAPPER_NAME = "train_utils.optimization.fastai_optim"
+OPTIM_STEP_TRAIN_NAME = "train_utils.train_utils"
+OPTIM_STEP = "modest_amd.utils.optim_step"             # step, clip_and_step and clip_grad_norm_ set by bind_optim_step()
 
 
 class StandIn(types.ModuleType):
@@ -317,6 +326,28 @@ def bind_batch_prep():
     if getattr(mods[0], "DatasetTemplate", None) is None or getattr(mods[1], "load_data_to_gpu", None) is None:
         return None
     importlib.import_module(BATCH_PREP).bind(mods[0].DatasetTemplate, mods[1])
+    return tuple(mods)
+
+
+def bind_optim_step():
+    """OptimWrapper.step / .clip_and_step of train_utils.optimization.fastai_optim and the name clip_grad_norm_ of
+    train_utils.train_utils := the three functions of modest_amd.utils.optim_step -- gradient clipping (two launches) and the
+    adam_onecycle optimiser step (one launch): three for the pair -- in the reference's modules if they are imported or can be (they are
+    importable only with the reference's ``tools/`` on ``sys.path``) -> (fastai_optim, train_utils), or None where either cannot be
+    imported or lacks its name.  A function of its own, opt-in: install() and what it returns stay as they are.  A wrapper around
+    anything but torch.optim.Adam with true weight decay reaches the method that was replaced.  Idempotent; touches no GPU state."""
+    mods = []
+    for name in (OPTIM_STEP_WRAPPER_NAME, OPTIM_STEP_TRAIN_NAME):
+        mod = sys.modules.get(name)
+        if mod is None:
+            try:
+                mod = importlib.import_module(name)
+            except ImportError:
+                return None
+        mods.append(mod)
+    if getattr(mods[0], "OptimWrapper", None) is None or getattr(mods[1], "clip_grad_norm_", None) is None:
+        return None
+    importlib.import_module(OPTIM_STEP).bind(mods[0].OptimWrapper, mods[1])
     return tuple(mods)
 
 
